@@ -10,13 +10,20 @@ window partial sums (1.5 KiB/rank) via all_gather over xGMI and every rank
 performs the deterministic rank-ordered combine — total work is fixed, so
 `scaling` is "strong" (the 1->8 GPU MSM scaling curve of the north star).
 
-Contract: rank 0 prints exactly ONE JSON line. The `roofline` object is
-measured live with HIP events on the library's own stream (the stream the
-kernels launch on); `traffic` is injected from the committed rocprofv3 PMC
-summary (profiles/roofline_traffic.json) when present, else null. The
-`cpu_baseline` leg times the OpenMP CPU oracle (a "port"-kind restatement of
-halo2curves best_multiexp — the reference itself is unbuildable here, see
-DESIGN.md) on the same inputs, rank 0 / N=1 only, bounded to a few reps.
+Contract: rank 0 prints exactly ONE JSON line. A plain run does only what
+the headline figure needs: set up, warm up, time `--steps` steps, optionally
+write the last step's result (`--dump-outputs DIR`), print the line; its
+`roofline` and `cpu_baseline` fields are null.
+
+`--full` adds the legs that take runs of their own: the warmup determinism
+check; the `roofline` object, measured live with HIP events on the library's
+own stream (the stream the kernels launch on), with `traffic` injected from
+the committed rocprofv3 PMC summary (profiles/roofline_traffic.json) when
+present, else null; and the `cpu_baseline` leg, which times the OpenMP CPU
+oracle (a "port"-kind restatement of halo2curves best_multiexp — the
+reference itself is unbuildable here) on the same inputs,
+rank 0 / N=1 only, bounded to a few reps, and cross-checks its result
+against the GPU's (`--no-cpu-baseline` skips this leg).
 """
 import argparse
 import json
@@ -39,18 +46,44 @@ def log(msg):
         print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
-def main():
+def dump_outputs(outdir, result):
+    """Write what the timed path returned in its last step as
+    DIR/<name>.npy. One step returns the MSM result: an affine G1 point as
+    64 bytes (x || y, little-endian Montgomery limbs). It is stored one
+    byte per float32 element (exact), so two builds compare element-wise."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arr = np.frombuffer(result, dtype=np.uint8).astype(np.float32)
+    np.save(os.path.join(outdir, "msm_result.npy"), arr)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: "
+                         "warmup determinism check, live roofline, CPU "
+                         "baseline + GPU-vs-CPU cross-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "result to DIR/msm_result.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="disable the two-slot async pipeline (A/B)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
-    import pywrap as oracle  # CPU oracle: cpu_baseline leg ONLY
+    import pywrap as oracle  # CPU oracle: input gen + cpu_baseline leg ONLY
     from spectre_amd import SpectreGpu, ffi
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -171,8 +204,9 @@ def main():
 
     # ---- warmup ----
     result = run_steps(max(args.warmup, 2))
-    check = run_steps(1)
-    assert result is None or check == result
+    if args.full:
+        check = run_steps(1)
+        assert result is None or check == result
 
     # ---- timed region ----
     if dist is not None:
@@ -191,9 +225,12 @@ def main():
     value = args.steps / elapsed  # whole-job MSM(2^20)/s (total work fixed)
     ms_per_step = elapsed * 1000.0 / args.steps
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
+
     # ---- roofline: dominant kernel (bucket accumulation), HIP events ----
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         _, st = gpu.msm_shard_device_timed(d_b, d_s, m)
         ent = st["real_entries"]
         # algorithmic bytes of k_bucket_acc per launch (DESIGN.md "Roofline"):
@@ -221,7 +258,7 @@ def main():
 
     # ---- CPU baseline: the OpenMP oracle, bounded sample ----
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline (OpenMP oracle Pippenger) ...")
         reps, tcpu = 0, 0.0
         while reps < 3 and tcpu < 10.0:
