@@ -23,8 +23,8 @@
  * failure; spectre_gpu_last_error() returns a thread-local message. The
  * library REQUIRES a visible AMD GPU for every compute entry point (there is
  * deliberately no CPU fallback — a missing GPU fails loudly); the only
- * host-only entry points are spectre_gpu_msm_g1_combine and the
- * format/version queries.
+ * host-only entry points are spectre_gpu_msm_g1_combine(_windows),
+ * spectre_gpu_msm_acc_auto_entries and the format/version queries.
  */
 #ifndef SPECTRE_GPU_H
 #define SPECTRE_GPU_H
@@ -118,6 +118,18 @@ int spectre_gpu_msm_g1_shard_device_async(spectre_gpu_ctx*, int dev,
                                           uint8_t* out_partials,
                                           int* out_slot);
 int spectre_gpu_msm_slot_wait(spectre_gpu_ctx*, int dev, int slot);
+/* Bucket accumulation gives every thread `e` consecutive sorted entries.
+ * e = 0 (the default) chooses it per call so that small inputs still put
+ * work on every compute unit; any other multiple of 4 up to
+ * SPECTRE_MSM_ACC_ENTRIES_MAX fixes it (tests, tuning). The result bytes do
+ * not depend on it. Applies to calls enqueued after it returns. */
+#define SPECTRE_MSM_ACC_ENTRIES_MAX (1u << 20)
+int spectre_gpu_set_msm_acc_entries(spectre_gpu_ctx*, uint32_t e);
+/* The auto rule itself (host-only, pure): entries per thread for `entries`
+ * sort entries on a device with `cus` compute units that keeps
+ * `resident_blocks` accumulate workgroups resident on each. */
+uint32_t spectre_gpu_msm_acc_auto_entries(uint64_t entries, uint32_t cus,
+                                          uint32_t resident_blocks);
 /* Combine gathered shard partials (host-only, deterministic rank order):
  * partials = nshards * NUM_WINDOWS * 96 B. */
 int spectre_gpu_msm_g1_combine(const uint8_t* partials, uint32_t nshards,

@@ -54,6 +54,13 @@ spectre_gpu_ctx* spectre_gpu_init(int device_count, const int* device_ids) {
         }
         ctx->devs.push_back(ds);
     }
+    // SPECTRE_MSM_ACC_E presets the entries per accumulate thread (tuning
+    // A/B from tools that do not call the setter); unusable values = auto
+    if (const char* e = getenv("SPECTRE_MSM_ACC_E")) {
+        const long v = atol(e);
+        if (v > 0 && !(v & 3) && v <= (long)SPECTRE_MSM_ACC_ENTRIES_MAX)
+            ctx->msm_acc_entries = (uint32_t)v;
+    }
     return ctx;
 }
 
@@ -96,6 +103,22 @@ void spectre_gpu_destroy(spectre_gpu_ctx* ctx) {
 
 int spectre_gpu_device_count(spectre_gpu_ctx* ctx) {
     return ctx ? (int)ctx->devs.size() : 0;
+}
+
+int spectre_gpu_set_msm_acc_entries(spectre_gpu_ctx* ctx, uint32_t e) {
+    if (!ctx || (e & 3) || e > SPECTRE_MSM_ACC_ENTRIES_MAX) {
+        set_err("set_msm_acc_entries: %u is not 0 or a multiple of 4 <= %u",
+                e, SPECTRE_MSM_ACC_ENTRIES_MAX);
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    ctx->msm_acc_entries = e;
+    return 0;
+}
+
+uint32_t spectre_gpu_msm_acc_auto_entries(uint64_t entries, uint32_t cus,
+                                          uint32_t resident_blocks) {
+    return msm_acc_auto_entries(entries, cus, resident_blocks);
 }
 
 // ---------------------------------------------------------------- staging

@@ -155,9 +155,11 @@ FF_HD void g1j_add_ip(g1_jac& p, const g1_jac& q) {
 // x = X/ZZ, y = Y/ZZZ with ZZ^3 == ZZZ^2. Mixed add (mADD-2008-s) is
 // 8M + 2S and ~4 add/sub vs Jacobian madd-2007-bl's 7M + 4S and ~7, BUT
 // using it as the k_bucket_acc accumulator (with per-run g1xyzz_to_jac
-// conversion) measured SLOWER on MI355X: 152 VGPRs / 3 waves/SIMD vs 84 /
-// 4-5 for the Jacobian form — bucket_acc 2.31 -> 3.09 ms at n=2^20. The
-// occupancy loss beats the ~9% multiply saving. Retained (bit-exact,
+// conversion) measured SLOWER on MI355X: bucket_acc 2.31 -> 3.09 ms at
+// n=2^20, despite ~9% fewer multiplies. (The r2 note blamed occupancy,
+// "152 VGPRs / 3 waves vs 84 / 4-5"; 84 was the profiler's half-count of
+// the Jacobian kernel's 168 allocated registers, which also run at 3
+// waves/SIMD, so the cause is not settled.) Retained (bit-exact,
 // unused on the hot path) for lower-pressure contexts. Identity: ZZ == 0.
 struct g1_xyzz {
     fp256 X, Y, ZZ, ZZZ;

@@ -27,9 +27,12 @@
 #ifndef MSM_CHUNK
 #define MSM_CHUNK 8                        // buckets per reduction thread
 #endif
-#ifndef MSM_ACC_E
-#define MSM_ACC_E 64                       // sorted entries per acc thread
-#endif
+// Sorted entries per accumulate thread are a per-call value (a multiple of
+// 4): ctx->msm_acc_entries when set, else msm_acc_auto_entries() within
+// these bounds.
+#define MSM_ACC_E_MIN 8
+#define MSM_ACC_E_MAX 64
+#define MSM_ACC_TARGET_BLOCKS 2            // accumulate blocks aimed at per CU
 
 struct NttPlan {
     fp256* tw1 = nullptr;  // butterfly twiddles, axis 1
@@ -61,10 +64,11 @@ struct MsmSlot {
     size_t nb_cap = 0;              // bucket-array capacity (batched)
     uint32_t* d_offsets = nullptr;  // nb_cap + 1
     g1_jac* d_buckets = nullptr;    // MSM_NB_TOTAL
-    uint32_t* d_firstK = nullptr;   // boundary-run side arrays (ent_cap/ACC_E)
+    uint32_t* d_firstK = nullptr;   // boundary-run side arrays (side_cap)
     uint32_t* d_lastK = nullptr;
     g1_jac* d_firstP = nullptr;
     g1_jac* d_lastP = nullptr;
+    size_t side_cap = 0;            // capacity in accumulate threads
     g1_jac* d_red = nullptr;        // reduction ping-pong (NB_TOTAL/CHUNK * 2)
     // Window sums come back through a PINNED per-slot buffer: an async D2H
     // into caller (pageable) memory silently blocks the calling thread on
@@ -81,6 +85,8 @@ struct DeviceState {
     hipStream_t stream = nullptr;
     MsmSlot slots[3];  // >=2 enables the async pipeline; 3rd for depth-3 A/B
     int next_slot = 0;  // round-robin for the async API
+    int num_cus = 0;              // filled with acc_resident_blocks
+    int acc_resident_blocks = 0;  // k_bucket_acc blocks resident per CU
     uint8_t* d_scalars = nullptr;
     size_t scal_cap = 0;  // bytes
     g1_affine* d_bases = nullptr;
@@ -110,6 +116,7 @@ struct DeviceState {
 struct spectre_gpu_ctx {
     std::vector<DeviceState> devs;
     std::recursive_mutex mu;
+    uint32_t msm_acc_entries = 0;  // entries per accumulate thread, 0 = auto
 };
 
 void set_err(const char* fmt, ...);
@@ -156,6 +163,10 @@ int msm_batch_windows_device(spectre_gpu_ctx* ctx, int dev,
                              uint32_t w_cnt, g1_jac* winsums_host,
                              double* stage_ms = nullptr, bool sync = true,
                              int slot = 0);
+
+// msm.hip — the auto rule for entries per accumulate thread (pure; host).
+uint32_t msm_acc_auto_entries(uint64_t entries, uint32_t cus,
+                              uint32_t resident_blocks);
 
 // msm.hip — sync a slot's stream and deliver pending window sums.
 int msm_slot_drain(spectre_gpu_ctx* ctx, int dev, int slot);

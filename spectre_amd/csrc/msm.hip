@@ -18,8 +18,10 @@
 //                         keys; zero digits get a sentinel key sorting last.
 //   3. k_bucket_offsets — binary-search segment bounds per bucket.
 //   4. k_bucket_acc     — equal-work partitioning: each thread owns exactly
-//                         MSM_ACC_E sorted entries (serial Jacobian+affine
-//                         mixed adds); interior runs write their bucket
+//                         E sorted entries, E chosen per call so small
+//                         inputs still fill the chip (serial Jacobian+affine
+//                         mixed adds, entry stream prefetched through LDS);
+//                         interior runs write their bucket
 //                         exclusively, boundary runs are merged by
 //                         k_bucket_fix. Deterministic by construction, and
 //                         the affine result is canonical, so ANY schedule
@@ -44,11 +46,15 @@
 // latency hiding comes from the serial-add structure, not occupancy
 // (measured: 1 add-chain/thread already saturates the VALU issue pipe).
 #define PT_KERNEL __global__ __launch_bounds__(THREADS, 2)
-// The accumulate/fix kernels have no LDS or barriers, so their block size
-// only sets the residency granule. MEASURED (r2): 64/128/256-thread blocks
-// are within run-to-run noise (acc 2.26-2.29 ms) — the 24% memory-parked
-// wave time (SQ_WAIT_ANY) does not yield to the extra wave 128-thread
-// blocks admit (84 VGPRs -> 5 waves/SIMD vs 4). Kept tunable.
+// The accumulate/fix kernels have no barriers (k_bucket_acc's LDS staging
+// is private to each wave, 8 KiB), so their block size only sets the
+// residency granule. MEASURED (r2): 64/128/256-thread blocks
+// are within run-to-run noise (acc 2.26-2.29 ms). The code object says
+// k_bucket_acc uses 165 VGPRs (168 allocated, 3 waves/SIMD; 163 before the
+// LDS-staged prefetch) — the profiler's VGPR column shows half the
+// allocation (84), which earlier notes misread as 4-5 waves/SIMD. One madd
+// chain per SIMD already fills the multiply issue pipe, so neither block
+// size nor residency moves the stage. Kept tunable.
 #ifndef MSM_ACC_THREADS
 #define MSM_ACC_THREADS 256
 #endif
@@ -127,55 +133,119 @@ __global__ void k_bucket_offsets(const uint32_t* __restrict__ keys,
 // ---- kernel 4: bucket accumulation, equal-work partitioning ---------------
 // Bucket sizes are Poisson(mean ent/NB); one-thread-per-bucket makes the
 // busiest lane in a wave ~1.5x the mean (SIMT runs at the max). Instead each
-// thread owns exactly MSM_ACC_E consecutive SORTED entries: runs that start
-// AND end strictly inside the range write their bucket directly (exclusive);
-// the first and last (potentially thread-spanning) runs go to side arrays
-// keyed by bucket, merged by k_bucket_fix.
+// thread owns exactly E consecutive SORTED entries (E is a per-call value,
+// a multiple of 4 — see msm_acc_auto_entries): runs that start AND end
+// strictly inside the range write their bucket directly (exclusive); the
+// first and last (potentially thread-spanning) runs go to side arrays keyed
+// by bucket, merged by k_bucket_fix.
+//
+// The entry stream is software-pipelined through LDS, so no global load sits
+// between two madds and the prefetched data costs no registers (holding the
+// next point in VGPRs across the madd drops the kernel to 2 waves/SIMD):
+//   * keys/values arrive in 16-byte quads (thread ranges start at multiples
+//     of 4 entries, so every quad is aligned), double-buffered: the quad
+//     after the current one is in flight while the current one is consumed;
+//   * the base point of entry i+1 is gathered BEFORE the madd of entry i,
+//     from a value that is already in LDS.
+// All of it uses the direct global->LDS load: each wave instruction writes
+// 16 B per lane at (wave-uniform base + lane * 16), the source address is per
+// lane. Per wave that is 8 KiB: 4 pieces of one affine point, 2x2 quads.
+// Every prefetch stays inside the thread's own range: quads are only read
+// while they hold at least one owned entry (the arrays are allocated in
+// whole quads), points only for owned entries. All owned entries are real:
+// off[nb_total] counts exactly the keys below the skip sentinel.
+#define ACC_WAVES (MSM_ACC_THREADS / 64)
+__device__ __forceinline__ void glds16(const void* src, uint4* wave_dst) {
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)src,
+        (__attribute__((address_space(3))) void*)wave_dst, 16, 0, 0);
+}
+// direct loads landed / LDS reads returned (the compiler does not order
+// either against the other kind of access to the same LDS bytes)
+__device__ __forceinline__ void glds_landed() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ void lds_reads_done() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 ACC_KERNEL void k_bucket_acc(const uint32_t* __restrict__ off,
                             const uint32_t* __restrict__ keys,
                             const uint32_t* __restrict__ vals,
                             const g1_affine* __restrict__ bases,
-                            uint32_t nb_total, g1_jac* __restrict__ buckets,
+                            uint32_t nb_total, uint32_t E,
+                            g1_jac* __restrict__ buckets,
                             uint32_t* __restrict__ firstK,
                             g1_jac* __restrict__ firstP,
                             uint32_t* __restrict__ lastK,
                             g1_jac* __restrict__ lastP) {
+    // [wave][slot][lane]: slots 0-3 point x|y, 4-5 key quads, 6-7 value quads
+    __shared__ uint4 stage[ACC_WAVES][8][64];
     const uint32_t ent = off[nb_total];  // real (non-skip) entries
-    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t lo = (uint64_t)t * MSM_ACC_E;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t lo = (uint64_t)t * E;
     if (lo >= ent) return;
-    uint64_t hi = lo + MSM_ACC_E;
-    if (hi > ent) hi = ent;
-    uint32_t k = keys[lo];
+    const uint32_t cnt = ent - lo < E ? (uint32_t)(ent - lo) : E;
+    const uint4* kq = (const uint4*)(keys + lo);
+    const uint4* vq = (const uint4*)(vals + lo);
+    const uint32_t lane = threadIdx.x & 63;
+    uint4(*st)[64] = stage[threadIdx.x >> 6];
+    glds16(kq, st[4]);
+    glds16(vq, st[6]);
+    glds_landed();
+    uint32_t k = st[4][lane].x;
+    {
+        // plain (cached) loads: bases are re-read by all 16 windows, so
+        // L1/L2 residency pays (non-temporal loads measured 5% slower)
+        const uint4* src = (const uint4*)(bases + (st[6][lane].x & 0x7fffffffu));
+        for (int c = 0; c < 4; c++) glds16(src + c, st[c]);
+    }
     // MEASURED NEGATIVE RESULT (r2): accumulating runs in XYZZ
     // (mADD-2008-s, 8M+2S — see g1.hpp) with a per-run Jacobian conversion
-    // is bit-exact but SLOWER: 152 VGPRs / 3 waves/SIMD vs the Jacobian
-    // accumulator's 84 / 4-5, and bucket_acc went 2.31 -> 3.09 ms at
-    // n=2^20 — the occupancy loss outweighs the ~9% fewer multiplies.
+    // is bit-exact but SLOWER (bucket_acc 2.31 -> 3.09 ms at n=2^20): the
+    // fewer multiplies do not pay for the larger accumulator.
     g1_jac acc;
     g1j_set_inf(acc);
     bool first = true;
-    for (uint64_t j = lo; j < hi; j++) {
-        uint32_t kj = keys[j];
+    for (uint32_t i = 0; i < cnt; i++) {
+        glds_landed();  // point i; quad issued at the previous multiple of 4
+        const uint32_t q = 4 + ((i >> 2) & 1);
+        const uint32_t kj = ((const uint32_t*)&st[q][lane])[i & 3];
+        const uint32_t v = ((const uint32_t*)&st[q + 2][lane])[i & 3];
+        g1_affine p;
+        {
+            const uint4 x0 = st[0][lane], x1 = st[1][lane];
+            const uint4 y0 = st[2][lane], y1 = st[3][lane];
+            p.x.l[0] = x0.x; p.x.l[1] = x0.y; p.x.l[2] = x0.z; p.x.l[3] = x0.w;
+            p.x.l[4] = x1.x; p.x.l[5] = x1.y; p.x.l[6] = x1.z; p.x.l[7] = x1.w;
+            p.y.l[0] = y0.x; p.y.l[1] = y0.y; p.y.l[2] = y0.z; p.y.l[3] = y0.w;
+            p.y.l[4] = y1.x; p.y.l[5] = y1.y; p.y.l[6] = y1.z; p.y.l[7] = y1.w;
+        }
+        if (i + 1 < cnt) {
+            const uint32_t qn = 6 + (((i + 1) >> 2) & 1);
+            const uint32_t vn = ((const uint32_t*)&st[qn][lane])[(i + 1) & 3];
+            lds_reads_done();  // before the slots read above are overwritten
+            if ((i & 3) == 0 && i + 4 < cnt) {  // quad after the current one
+                const uint32_t qf = 4 + (((i >> 2) + 1) & 1);
+                glds16(kq + (i >> 2) + 1, st[qf]);
+                glds16(vq + (i >> 2) + 1, st[qf + 2]);
+            }
+            const uint4* src = (const uint4*)(bases + (vn & 0x7fffffffu));
+            for (int c = 0; c < 4; c++) glds16(src + c, st[c]);
+        }
         if (kj != k) {  // flush completed run
             if (first) {
                 firstK[t] = k;
                 firstP[t] = acc;
                 first = false;
-            } else if (k < nb_total) {
+            } else {
                 buckets[k] = acc;  // interior run: exclusive writer
             }
             g1j_set_inf(acc);
             k = kj;
         }
-        if (kj < nb_total) {
-            uint32_t v = vals[j];
-            // plain (cached) loads: bases are re-read by all 16 windows, so
-            // L1/L2 residency pays (non-temporal loads measured 5% slower)
-            g1_affine p = bases[v & 0x7fffffffu];
-            if (v & 0x80000000u) ff_neg<Fq>(p.y, p.y);
-            g1j_madd_ip(acc, p);
-        }
+        if (v & 0x80000000u) ff_neg<Fq>(p.y, p.y);
+        g1j_madd_ip(acc, p);
     }
     if (first) {  // whole range is one run
         firstK[t] = k;
@@ -194,7 +264,8 @@ ACC_KERNEL void k_bucket_fix(const uint32_t* __restrict__ off,
                             const g1_jac* __restrict__ firstP,
                             const uint32_t* __restrict__ lastK,
                             const g1_jac* __restrict__ lastP,
-                            uint32_t nb_total, g1_jac* __restrict__ buckets) {
+                            uint32_t nb_total, uint32_t E,
+                            g1_jac* __restrict__ buckets) {
     uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb_total) return;
     uint32_t s = off[b], e = off[b + 1];
@@ -202,13 +273,13 @@ ACC_KERNEL void k_bucket_fix(const uint32_t* __restrict__ off,
         g1j_set_inf(buckets[b]);
         return;
     }
-    uint32_t ts = s / MSM_ACC_E, te = (e - 1) / MSM_ACC_E;
+    uint32_t ts = s / E, te = (e - 1) / E;
     // interior (already written by its exclusive thread) iff the run starts
     // after the thread's range start AND ends before the thread's range end —
     // note a run ending at the END OF DATA (e == ent) ended the thread's
     // loop, so it lives in lastP, not in buckets[].
     const uint32_t ent = off[nb_total];
-    if (ts == te && (s % MSM_ACC_E) && (e % MSM_ACC_E) && e != ent)
+    if (ts == te && (s % E) && (e % E) && e != ent)
         return;
     g1_jac acc;
     g1j_set_inf(acc);
@@ -284,8 +355,50 @@ __global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_sum(
 }
 
 // ---- host orchestration ---------------------------------------------------
+// Entries per accumulate thread when the caller has not fixed one.
+// MEASURED on MI355X (n = 2^20, accumulate + fix stage): one madd chain per
+// SIMD already fills the integer-multiply issue pipe, so the stage costs the
+// same 2.23-2.25 ms for E = 32, 44, 64 whether or not the grid is a whole
+// number of resident rounds, and MORE for one exact round (E = 88: 2.38 ms;
+// half a round, E = 176: 3.16 ms): the dispatcher balances many short
+// blocks better than equal shares balance themselves. So large inputs keep
+// E = MSM_ACC_E_MAX. Small inputs are where E matters: at n = 2^16 the
+// stage takes 0.91 ms at E = 64 (64 blocks on 256 CUs), 0.52 at 32, 0.32 at
+// 16, 0.29 at 8 and 0.37 at 4, where the two boundary partials per thread
+// that k_bucket_fix merges start to cost more than the parallelism gives.
+// The rule: aim for MSM_ACC_TARGET_BLOCKS resident blocks on every CU
+// (fewer if fewer fit), E rounded up to the quad the kernel loads, within
+// [MSM_ACC_E_MIN, MSM_ACC_E_MAX].
+uint32_t msm_acc_auto_entries(uint64_t entries, uint32_t cus,
+                              uint32_t resident_blocks) {
+    uint32_t per_cu = resident_blocks ? resident_blocks : 1;
+    if (per_cu > MSM_ACC_TARGET_BLOCKS) per_cu = MSM_ACC_TARGET_BLOCKS;
+    const uint64_t threads =
+        (uint64_t)(cus ? cus : 1) * per_cu * MSM_ACC_THREADS;
+    if (entries >= threads * MSM_ACC_E_MAX) return MSM_ACC_E_MAX;
+    uint64_t e = (entries + threads - 1) / threads;
+    e = (e + 3) & ~3ull;
+    if (e < MSM_ACC_E_MIN) e = MSM_ACC_E_MIN;
+    if (e > MSM_ACC_E_MAX) e = MSM_ACC_E_MAX;
+    return (uint32_t)e;
+}
+
+// CUs and resident k_bucket_acc blocks per CU, once per device.
+static int ensure_acc_geometry(DeviceState& dstate) {
+    if (dstate.acc_resident_blocks) return 0;
+    int cus = 0, nb = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  dstate.device_id));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &nb, k_bucket_acc, MSM_ACC_THREADS, 0));
+    dstate.num_cus = cus > 0 ? cus : 1;
+    dstate.acc_resident_blocks = nb > 0 ? nb : 1;
+    return 0;
+}
+
 static int ensure_msm_scratch(MsmSlot& ds, hipStream_t stream, uint64_t n,
-                              uint32_t nbatch, uint32_t w_cnt) {
+                              uint32_t nbatch, uint32_t w_cnt,
+                              uint32_t acc_e) {
     const uint64_t ent = (uint64_t)nbatch * w_cnt * n;
     const uint64_t nbt = (uint64_t)nbatch * w_cnt * MSM_BPW;
     if (ds.ent_cap < ent) {
@@ -294,20 +407,28 @@ static int ensure_msm_scratch(MsmSlot& ds, hipStream_t stream, uint64_t n,
         // only advanced after every allocation in the group succeeds).
         ds.ent_cap = 0;
         for (void** p : {(void**)&ds.d_keys_in, (void**)&ds.d_keys_out,
-                         (void**)&ds.d_vals_in, (void**)&ds.d_vals_out,
-                         (void**)&ds.d_firstK, (void**)&ds.d_lastK,
+                         (void**)&ds.d_vals_in, (void**)&ds.d_vals_out})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        // whole quads: k_bucket_acc reads keys/values 16 bytes at a time
+        const uint64_t ent4 = (ent + 3) & ~3ull;
+        HIP_TRY(hipMalloc(&ds.d_keys_in, ent4 * 4));
+        HIP_TRY(hipMalloc(&ds.d_keys_out, ent4 * 4));
+        HIP_TRY(hipMalloc(&ds.d_vals_in, ent4 * 4));
+        HIP_TRY(hipMalloc(&ds.d_vals_out, ent4 * 4));
+        ds.ent_cap = ent;
+    }
+    // boundary-run side arrays: one slot per accumulate thread of THIS call
+    const uint64_t nt = (ent + acc_e - 1) / acc_e;
+    if (ds.side_cap < nt) {
+        ds.side_cap = 0;
+        for (void** p : {(void**)&ds.d_firstK, (void**)&ds.d_lastK,
                          (void**)&ds.d_firstP, (void**)&ds.d_lastP})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
-        HIP_TRY(hipMalloc(&ds.d_keys_in, ent * 4));
-        HIP_TRY(hipMalloc(&ds.d_keys_out, ent * 4));
-        HIP_TRY(hipMalloc(&ds.d_vals_in, ent * 4));
-        HIP_TRY(hipMalloc(&ds.d_vals_out, ent * 4));
-        const uint64_t nt = (ent + MSM_ACC_E - 1) / MSM_ACC_E;
         HIP_TRY(hipMalloc(&ds.d_firstK, nt * 4));
         HIP_TRY(hipMalloc(&ds.d_lastK, nt * 4));
         HIP_TRY(hipMalloc(&ds.d_firstP, nt * sizeof(g1_jac)));
         HIP_TRY(hipMalloc(&ds.d_lastP, nt * sizeof(g1_jac)));
-        ds.ent_cap = ent;
+        ds.side_cap = nt;
     }
     if (ds.nb_cap < nbt) {
         ds.nb_cap = 0;
@@ -400,9 +521,16 @@ int msm_batch_windows_device(spectre_gpu_ctx* ctx, int dev,
             g1j_set_inf(winsums_host[w]);
         return 0;
     }
-    int rc = ensure_msm_scratch(ds, ds.stream, n, nbatch, w_cnt);
-    if (rc) return rc;
     const uint64_t ent = (uint64_t)nbatch * w_cnt * n;
+    int rc = ensure_acc_geometry(dstate);
+    if (rc) return rc;
+    const uint32_t acc_e =
+        ctx->msm_acc_entries
+            ? ctx->msm_acc_entries
+            : msm_acc_auto_entries(ent, (uint32_t)dstate.num_cus,
+                                   (uint32_t)dstate.acc_resident_blocks);
+    rc = ensure_msm_scratch(ds, ds.stream, n, nbatch, w_cnt, acc_e);
+    if (rc) return rc;
     const uint32_t nbt = nbatch * w_cnt * MSM_BPW;
     const int canonical = (flags & SPECTRE_SCALARS_CANONICAL) ? 1 : 0;
     hipStream_t st = ds.stream;
@@ -430,18 +558,18 @@ int msm_batch_windows_device(spectre_gpu_ctx* ctx, int dev,
                        dim3((nbt + 1 + THREADS - 1) / THREADS), dim3(THREADS),
                        0, st, ds.d_keys_out, ent, nbt, ds.d_offsets);
     STAMP(3);
-    const uint32_t nt_acc = (uint32_t)((ent + MSM_ACC_E - 1) / MSM_ACC_E);
+    const uint32_t nt_acc = (uint32_t)((ent + acc_e - 1) / acc_e);
     hipLaunchKernelGGL(k_bucket_acc,
                        dim3((nt_acc + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS),
                        dim3(MSM_ACC_THREADS), 0, st, ds.d_offsets,
-                       ds.d_keys_out, ds.d_vals_out, d_bases, nbt,
+                       ds.d_keys_out, ds.d_vals_out, d_bases, nbt, acc_e,
                        ds.d_buckets, ds.d_firstK, ds.d_firstP, ds.d_lastK,
                        ds.d_lastP);
     hipLaunchKernelGGL(k_bucket_fix,
                        dim3((nbt + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS),
                        dim3(MSM_ACC_THREADS), 0, st, ds.d_offsets,
                        ds.d_firstK, ds.d_firstP, ds.d_lastK, ds.d_lastP, nbt,
-                       ds.d_buckets);
+                       acc_e, ds.d_buckets);
     STAMP(4);
     const uint32_t nchunks = nbt / MSM_CHUNK;
     g1_jac* red0 = ds.d_red;

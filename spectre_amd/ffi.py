@@ -18,6 +18,10 @@ WINDOW_BITS = 16  # = SPECTRE_MSM_WINDOW_BITS
 NUM_WINDOWS = 16  # = SPECTRE_MSM_NUM_WINDOWS
 NUM_BUCKETS = NUM_WINDOWS * (1 << (WINDOW_BITS - 1))
 PARTIALS_BYTES = NUM_WINDOWS * 96  # per-shard Jacobian window sums
+MSM_ACC_THREADS = 256  # bucket-accumulate workgroup size
+MSM_ACC_E_MIN = 8      # bounds of the auto entries-per-thread rule
+MSM_ACC_E_MAX = 64     # (= MSM_ACC_E_MIN / MSM_ACC_E_MAX in csrc/internal.hpp)
+MSM_ACC_TARGET_BLOCKS = 2  # accumulate blocks the rule aims at per CU
 
 _lib = None
 
@@ -82,6 +86,12 @@ def load_library() -> ctypes.CDLL:
     ]
     lib.spectre_gpu_msm_slot_wait.restype = c.c_int
     lib.spectre_gpu_msm_slot_wait.argtypes = [c.c_void_p, c.c_int, c.c_int]
+    lib.spectre_gpu_set_msm_acc_entries.restype = c.c_int
+    lib.spectre_gpu_set_msm_acc_entries.argtypes = [c.c_void_p, c.c_uint32]
+    lib.spectre_gpu_msm_acc_auto_entries.restype = c.c_uint32
+    lib.spectre_gpu_msm_acc_auto_entries.argtypes = [
+        c.c_uint64, c.c_uint32, c.c_uint32,
+    ]
     lib.spectre_gpu_msm_g1_shard_windows_device.restype = c.c_int
     lib.spectre_gpu_msm_g1_shard_windows_device.argtypes = [
         c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint32,
@@ -137,6 +147,13 @@ def load_library() -> ctypes.CDLL:
 
 def version() -> str:
     return load_library().spectre_gpu_version().decode()
+
+
+def msm_acc_auto_entries(entries: int, cus: int, resident_blocks: int) -> int:
+    """Host-only: the library's auto rule for sorted entries per bucket
+    accumulate thread (see spectre_gpu_set_msm_acc_entries)."""
+    return load_library().spectre_gpu_msm_acc_auto_entries(
+        entries, cus, resident_blocks)
 
 
 def combine_window_partials(partials: bytes, nshards: int) -> bytes:
@@ -288,6 +305,12 @@ class SpectreGpu:
             ctypes.byref(slot))
         self._check(rc, "msm_g1_shard_device_async")
         return out, slot.value
+
+    def set_msm_acc_entries(self, e: int) -> None:
+        """Fix the sorted entries per bucket-accumulate thread (a multiple
+        of 4); 0 restores the per-call auto choice. Results do not change."""
+        rc = self._lib.spectre_gpu_set_msm_acc_entries(self._ctx, e)
+        self._check(rc, "set_msm_acc_entries")
 
     def msm_slot_wait(self, slot: int, dev: int = 0) -> None:
         rc = self._lib.spectre_gpu_msm_slot_wait(self._ctx, dev, slot)
