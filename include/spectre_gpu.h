@@ -103,14 +103,15 @@ int spectre_gpu_msm_g1_shard_device_timed(spectre_gpu_ctx*, int dev,
                                           uint32_t flags,
                                           uint8_t* out_partials,
                                           double out_ms[8]);
-/* Pipelined (async) shard MSM: enqueue the full pipeline on one of two
+/* Pipelined (async) shard MSM: enqueue the full pipeline on one of three
  * per-device slots (own stream + scratch) and return WITHOUT synchronizing;
- * *out_slot receives the slot id. Back-to-back MSMs on alternating slots
+ * *out_slot receives the slot id. Back-to-back MSMs on successive slots
  * overlap call i's latency-bound reduction tail with call i+1's
  * digits/sort/accumulate (create_proof's ~45 commits per proof arrive
  * exactly this way). out_partials (NUM_WINDOWS * 96 B) must stay valid
  * until spectre_gpu_msm_slot_wait(ctx, dev, slot) returns. At most one
- * call may be in flight per slot. */
+ * call may be in flight per slot: a further one fails with -3, and so does
+ * a synchronous MSM (they run on slot 0) while slot 0 has one in flight. */
 int spectre_gpu_msm_g1_shard_device_async(spectre_gpu_ctx*, int dev,
                                           const void* d_bases,
                                           const void* d_scalars, uint64_t n,

@@ -68,35 +68,7 @@ void spectre_gpu_destroy(spectre_gpu_ctx* ctx) {
     if (!ctx) return;
     for (auto& ds : ctx->devs) {
         (void)hipSetDevice(ds.device_id);
-        for (auto& sl : ds.slots) {
-            for (void* p : {(void*)sl.d_keys_in, (void*)sl.d_keys_out,
-                            (void*)sl.d_vals_in, (void*)sl.d_vals_out,
-                            (void*)sl.d_sort_tmp, (void*)sl.d_offsets,
-                            (void*)sl.d_buckets, (void*)sl.d_firstK,
-                            (void*)sl.d_lastK, (void*)sl.d_firstP,
-                            (void*)sl.d_lastP, (void*)sl.d_red})
-                if (p) (void)hipFree(p);
-            if (sl.h_wins) (void)hipHostFree(sl.h_wins);
-            if (sl.stream && sl.stream != ds.stream)
-                (void)hipStreamDestroy(sl.stream);
-        }
-        for (void* p : {(void*)ds.d_scalars, (void*)ds.d_bases,
-                        (void*)ds.d_ntt_tmp, (void*)ds.d_ntt_io,
-                        (void*)ds.d_cosetA})
-            if (p) (void)hipFree(p);
-        for (int i = 0; i < 2; i++) {
-            if (ds.h_stage[i]) (void)hipHostFree(ds.h_stage[i]);
-            if (ds.stage_ev[i]) (void)hipEventDestroy(ds.stage_ev[i]);
-        }
-        for (auto& kv : ds.bases_cache)
-            if (kv.second.d_ptr) (void)hipFree(kv.second.d_ptr);
-        for (auto& kv : ds.plans) {
-            if (kv.second.tw1) (void)hipFree(kv.second.tw1);
-            if (kv.second.tw2) (void)hipFree(kv.second.tw2);
-            if (kv.second.tw3) (void)hipFree(kv.second.tw3);
-            if (kv.second.twB) (void)hipFree(kv.second.twB);
-        }
-        if (ds.stream) (void)hipStreamDestroy(ds.stream);
+        ds.release();
     }
     delete ctx;
 }
@@ -125,35 +97,31 @@ uint32_t spectre_gpu_msm_acc_auto_entries(uint64_t entries, uint32_t cus,
 #define STAGE_CHUNK (16u << 20)
 
 static int ensure_stage(DeviceState& ds) {
-    if (!ds.h_stage[0]) {
-        HIP_TRY(hipHostMalloc((void**)&ds.h_stage[0], STAGE_CHUNK));
-        HIP_TRY(hipHostMalloc((void**)&ds.h_stage[1], STAGE_CHUNK));
-        HIP_TRY(hipEventCreate(&ds.stage_ev[0]));
-        HIP_TRY(hipEventCreate(&ds.stage_ev[1]));
-        HIP_TRY(hipEventRecord(ds.stage_ev[0], ds.stream));
-        HIP_TRY(hipEventRecord(ds.stage_ev[1], ds.stream));
+    for (int b = 0; b < 2; b++) {
+        RC_TRY(ds.h_stage[b].reserve(STAGE_CHUNK));
+        if (ds.stage_ev[b]) continue;
+        HIP_TRY(hipEventCreate(&ds.stage_ev[b]));
+        HIP_TRY(hipEventRecord(ds.stage_ev[b], ds.stream));
     }
     return 0;
 }
 
-// host->device through alternating pinned chunks: memcpy of chunk k+1
-// overlaps the DMA of chunk k; the stream stays ordered so following
-// kernels need no extra sync. The user buffer is fully consumed by the
-// memcpys before return (the in-flight DMA reads only pinned memory).
-// double-buffered pinned-staging copies on ds.stream: pageable hipMemcpy
-// runs at ~3 GB/s; staging through pinned chunks overlaps the host memcpy
-// with the DMA and reaches ~3-4x that.
+// host->device on ds.stream through alternating pinned chunks: pageable
+// hipMemcpy runs at ~3 GB/s; here the memcpy of chunk k+1 overlaps the DMA
+// of chunk k, which reaches ~3-4x that. The stream stays ordered, so
+// following kernels need no extra sync, and the user buffer is fully
+// consumed by the memcpys before return (the in-flight DMA reads only
+// pinned memory).
 static int staged_upload(DeviceState& ds, void* d_dst, const void* src,
                          size_t bytes) {
-    int rc = ensure_stage(ds);
-    if (rc) return rc;
+    RC_TRY(ensure_stage(ds));
     size_t off = 0;
     int b = 0;
     while (off < bytes) {
         const size_t len = bytes - off < STAGE_CHUNK ? bytes - off : STAGE_CHUNK;
         HIP_TRY(hipEventSynchronize(ds.stage_ev[b]));  // buffer free?
-        memcpy(ds.h_stage[b], (const uint8_t*)src + off, len);
-        HIP_TRY(hipMemcpyAsync((uint8_t*)d_dst + off, ds.h_stage[b], len,
+        memcpy(ds.h_stage[b].ptr, (const uint8_t*)src + off, len);
+        HIP_TRY(hipMemcpyAsync((uint8_t*)d_dst + off, ds.h_stage[b].ptr, len,
                                hipMemcpyHostToDevice, ds.stream));
         HIP_TRY(hipEventRecord(ds.stage_ev[b], ds.stream));
         off += len;
@@ -164,8 +132,7 @@ static int staged_upload(DeviceState& ds, void* d_dst, const void* src,
 
 static int staged_download(DeviceState& ds, void* dst, const void* d_src,
                            size_t bytes) {
-    int rc = ensure_stage(ds);
-    if (rc) return rc;
+    RC_TRY(ensure_stage(ds));
     size_t off = 0;
     int b = 0;
     size_t pend_off[2] = {0, 0}, pend_len[2] = {0, 0};
@@ -173,10 +140,11 @@ static int staged_download(DeviceState& ds, void* dst, const void* d_src,
         const size_t len = bytes - off < STAGE_CHUNK ? bytes - off : STAGE_CHUNK;
         if (pend_len[b]) {  // drain the older use of this buffer
             HIP_TRY(hipEventSynchronize(ds.stage_ev[b]));
-            memcpy((uint8_t*)dst + pend_off[b], ds.h_stage[b], pend_len[b]);
+            memcpy((uint8_t*)dst + pend_off[b], ds.h_stage[b].ptr,
+                   pend_len[b]);
         }
-        HIP_TRY(hipMemcpyAsync(ds.h_stage[b], (const uint8_t*)d_src + off, len,
-                               hipMemcpyDeviceToHost, ds.stream));
+        HIP_TRY(hipMemcpyAsync(ds.h_stage[b].ptr, (const uint8_t*)d_src + off,
+                               len, hipMemcpyDeviceToHost, ds.stream));
         HIP_TRY(hipEventRecord(ds.stage_ev[b], ds.stream));
         pend_off[b] = off;
         pend_len[b] = len;
@@ -186,7 +154,8 @@ static int staged_download(DeviceState& ds, void* dst, const void* d_src,
     for (int i = 0; i < 2; i++) {
         if (pend_len[i]) {
             HIP_TRY(hipEventSynchronize(ds.stage_ev[i]));
-            memcpy((uint8_t*)dst + pend_off[i], ds.h_stage[i], pend_len[i]);
+            memcpy((uint8_t*)dst + pend_off[i], ds.h_stage[i].ptr,
+                   pend_len[i]);
         }
     }
     return 0;
@@ -241,15 +210,35 @@ int spectre_gpu_msm_g1_combine(const uint8_t* partials, uint32_t nshards,
 }
 
 // ---------------------------------------------------------------- MSM
+// a full-window-range call description
+static MsmCall msm_call(const void* d_bases, const void* d_scalars,
+                        uint32_t nbatch, uint64_t n, uint32_t flags) {
+    return {(const g1_affine*)d_bases, (const uint8_t*)d_scalars, nbatch, n,
+            flags, 0, MSM_NWIN};
+}
+
+// Round-robin slot for the async entry points. Measured on MI355X (r2):
+// depth 3 = 325.6 MSM(2^20)/s vs depth 2 = 300 vs unpipelined = 240 — three
+// in flight keep the machine fed through each call's host-combine + sync
+// gap, so every slot is used unless SPECTRE_PIPE_SLOTS asks for fewer.
+static int next_async_slot(DeviceState& ds) {
+    static const int kSlots = []() {
+        const char* e = getenv("SPECTRE_PIPE_SLOTS");
+        const int v = e ? atoi(e) : MSM_SLOTS;
+        return v < 1 ? 1 : (v > MSM_SLOTS ? MSM_SLOTS : v);
+    }();
+    const int slot = ds.next_slot;
+    ds.next_slot = (slot + 1) % kSlots;
+    return slot;
+}
+
 int spectre_gpu_msm_g1_shard_device(spectre_gpu_ctx* ctx, int dev,
                                     const void* d_bases, const void* d_scalars,
                                     uint64_t n, uint32_t flags,
                                     uint8_t* out_partials) {
-    if (check_dev(ctx, dev)) return -1;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    return msm_shard_device(ctx, dev, (const g1_affine*)d_bases,
-                            (const uint8_t*)d_scalars, n, flags,
-                            (g1_jac*)out_partials);
+    return spectre_gpu_msm_g1_shard_device_timed(ctx, dev, d_bases, d_scalars,
+                                                 n, flags, out_partials,
+                                                 nullptr);
 }
 
 int spectre_gpu_msm_g1_shard_device_timed(spectre_gpu_ctx* ctx, int dev,
@@ -260,9 +249,8 @@ int spectre_gpu_msm_g1_shard_device_timed(spectre_gpu_ctx* ctx, int dev,
                                           double out_ms[8]) {
     if (check_dev(ctx, dev)) return -1;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    return msm_shard_device(ctx, dev, (const g1_affine*)d_bases,
-                            (const uint8_t*)d_scalars, n, flags,
-                            (g1_jac*)out_partials, out_ms);
+    return msm_device(ctx, dev, msm_call(d_bases, d_scalars, 1, n, flags),
+                      (g1_jac*)out_partials, out_ms, /*sync=*/true, 0);
 }
 
 int spectre_gpu_msm_g1_shard_device_async(spectre_gpu_ctx* ctx, int dev,
@@ -271,24 +259,9 @@ int spectre_gpu_msm_g1_shard_device_async(spectre_gpu_ctx* ctx, int dev,
                                           uint32_t flags,
                                           uint8_t* out_partials,
                                           int* out_slot) {
-    if (check_dev(ctx, dev)) return -1;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    DeviceState& ds = ctx->devs[dev];
-    // measured on MI355X (r2): depth 3 = 325.6 MSM(2^20)/s vs depth 2 =
-    // 300 vs unpipelined = 240 — three in flight keep the machine fed
-    // through each call's host-combine + sync gap.
-    static const int kSlots = []() {
-        const char* e = getenv("SPECTRE_PIPE_SLOTS");
-        int v = e ? atoi(e) : 3;
-        return v < 1 ? 1 : (v > 3 ? 3 : v);
-    }();
-    const int slot = ds.next_slot;
-    ds.next_slot = (ds.next_slot + 1) % kSlots;
-    *out_slot = slot;
-    return msm_batch_shard_device(ctx, dev, (const g1_affine*)d_bases,
-                                  (const uint8_t*)d_scalars, 1, n, flags,
-                                  (g1_jac*)out_partials, nullptr,
-                                  /*sync=*/false, slot);
+    return spectre_gpu_msm_g1_shard_windows_device_async(
+        ctx, dev, d_bases, d_scalars, n, flags, 0, MSM_NWIN, out_partials,
+        out_slot);
 }
 
 // window-sharded multi-GPU: rank r of R computes windows
@@ -301,9 +274,11 @@ int spectre_gpu_msm_g1_shard_windows_device(spectre_gpu_ctx* ctx, int dev,
                                             uint8_t* out_partials) {
     if (check_dev(ctx, dev)) return -1;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    return msm_batch_windows_device(ctx, dev, (const g1_affine*)d_bases,
-                                    (const uint8_t*)d_scalars, 1, n, flags,
-                                    w_lo, w_cnt, (g1_jac*)out_partials);
+    MsmCall call = msm_call(d_bases, d_scalars, 1, n, flags);
+    call.w_lo = w_lo;
+    call.w_cnt = w_cnt;
+    return msm_device(ctx, dev, call, (g1_jac*)out_partials, nullptr,
+                      /*sync=*/true, 0);
 }
 
 int spectre_gpu_msm_g1_shard_windows_device_async(
@@ -312,19 +287,12 @@ int spectre_gpu_msm_g1_shard_windows_device_async(
     uint8_t* out_partials, int* out_slot) {
     if (check_dev(ctx, dev)) return -1;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    DeviceState& ds = ctx->devs[dev];
-    static const int kSlots = []() {
-        const char* e = getenv("SPECTRE_PIPE_SLOTS");
-        int v = e ? atoi(e) : 3;
-        return v < 1 ? 1 : (v > 3 ? 3 : v);
-    }();
-    const int slot = ds.next_slot;
-    ds.next_slot = (ds.next_slot + 1) % kSlots;
-    *out_slot = slot;
-    return msm_batch_windows_device(ctx, dev, (const g1_affine*)d_bases,
-                                    (const uint8_t*)d_scalars, 1, n, flags,
-                                    w_lo, w_cnt, (g1_jac*)out_partials,
-                                    nullptr, /*sync=*/false, slot);
+    MsmCall call = msm_call(d_bases, d_scalars, 1, n, flags);
+    call.w_lo = w_lo;
+    call.w_cnt = w_cnt;
+    *out_slot = next_async_slot(ctx->devs[dev]);
+    return msm_device(ctx, dev, call, (g1_jac*)out_partials, nullptr,
+                      /*sync=*/false, *out_slot);
 }
 
 // assemble disjoint per-shard window slices (shard i = NWIN/nshards
@@ -342,7 +310,7 @@ int spectre_gpu_msm_g1_combine_windows(const uint8_t* partials,
 
 int spectre_gpu_msm_slot_wait(spectre_gpu_ctx* ctx, int dev, int slot) {
     if (check_dev(ctx, dev)) return -1;
-    if (slot < 0 || slot > 2) {
+    if (slot < 0 || slot >= MSM_SLOTS) {
         set_err("slot_wait: slot %d out of range", slot);
         return -1;
     }
@@ -354,14 +322,8 @@ int spectre_gpu_msm_g1_device(spectre_gpu_ctx* ctx, int dev,
                               const void* d_bases, const void* d_scalars,
                               uint64_t n, uint32_t flags,
                               uint8_t out_affine[64]) {
-    if (check_dev(ctx, dev)) return -1;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    g1_jac wins[MSM_NWIN];
-    int rc = msm_shard_device(ctx, dev, (const g1_affine*)d_bases,
-                              (const uint8_t*)d_scalars, n, flags, wins);
-    if (rc) return rc;
-    winsums_to_affine(wins, out_affine);
-    return 0;
+    return spectre_gpu_msm_g1_batch_device(ctx, dev, d_bases, d_scalars, 1, n,
+                                           flags, out_affine);
 }
 
 int spectre_gpu_msm_g1_batch_device(spectre_gpu_ctx* ctx, int dev,
@@ -372,13 +334,53 @@ int spectre_gpu_msm_g1_batch_device(spectre_gpu_ctx* ctx, int dev,
     if (check_dev(ctx, dev)) return -1;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     std::vector<g1_jac> wins((size_t)nbatch * MSM_NWIN);
-    int rc = msm_batch_shard_device(ctx, dev, (const g1_affine*)d_bases,
-                                    (const uint8_t*)d_scalars, nbatch, n,
-                                    flags, wins.data());
-    if (rc) return rc;
+    RC_TRY(msm_device(ctx, dev, msm_call(d_bases, d_scalars, nbatch, n, flags),
+                      wins.data(), nullptr, /*sync=*/true, 0));
     for (uint32_t b = 0; b < nbatch; b++)
         winsums_to_affine(&wins[(size_t)b * MSM_NWIN], out_affine + 64 * b);
     return 0;
+}
+
+// scalars of a host-pointer call: plain scratch upload
+static int upload_scalars(DeviceState& ds, const uint8_t* src, size_t bytes) {
+    RC_TRY(ds.d_scalars.reserve(bytes));
+    return staged_upload(ds, ds.d_scalars.ptr, src, bytes);
+}
+
+// Device pointer to the `count` bases at src: the cache entry of (bases_id,
+// total_n, layout) when bases_id != 0 — uploaded on a miss, src may be NULL
+// on a hit — else the uncached scratch buffer. A device's chunk of a
+// sharded set depends on all three key words.
+static int resolve_bases(DeviceState& ds, uint64_t bases_id, uint64_t layout,
+                         uint64_t total_n, const uint8_t* src, uint64_t count,
+                         const g1_affine** d_out) {
+    const std::array<uint64_t, 3> key{bases_id, total_n, layout};
+    DevBuf<g1_affine>* buf = &ds.d_bases;
+    if (bases_id != 0) {
+        auto it = ds.bases_cache.find(key);
+        if (it != ds.bases_cache.end()) {
+            *d_out = it->second.ptr;
+            return 0;
+        }
+        if (!src) {
+            set_err("bases_id %llu not cached and bases is NULL",
+                    (unsigned long long)bases_id);
+            return -4;
+        }
+        buf = &ds.bases_cache[key];
+    } else if (!src) {
+        set_err("bases is NULL");
+        return -1;
+    }
+    int rc = buf->reserve(count);
+    if (rc == 0) rc = staged_upload(ds, buf->ptr, src, count * 64);
+    if (rc == 0) {
+        *d_out = buf->ptr;
+    } else if (bases_id != 0) {  // never cache a half-uploaded entry
+        buf->release();
+        ds.bases_cache.erase(key);
+    }
+    return rc;
 }
 
 int spectre_gpu_msm_g1_batch(spectre_gpu_ctx* ctx, uint64_t bases_id,
@@ -400,52 +402,11 @@ int spectre_gpu_msm_g1_batch(spectre_gpu_ctx* ctx, uint64_t bases_id,
     }
     DeviceState& ds = ctx->devs[0];
     HIP_TRY(hipSetDevice(ds.device_id));
-    const uint64_t sbytes = (uint64_t)nbatch * n * 32;
-    if (ds.scal_cap < sbytes) {
-        if (ds.d_scalars) (void)hipFree(ds.d_scalars);
-        HIP_TRY(hipMalloc(&ds.d_scalars, sbytes));
-        ds.scal_cap = sbytes;
-    }
-    {
-        int rc = staged_upload(ds, ds.d_scalars, scalars, sbytes);
-        if (rc) return rc;
-    }
-    g1_affine* d_b = nullptr;
-    if (bases_id != 0) {
-        std::array<uint64_t, 3> key{bases_id, n, 1};
-        auto it = ds.bases_cache.find(key);
-        if (it != ds.bases_cache.end()) {
-            d_b = it->second.d_ptr;
-        } else {
-            if (!bases) {
-                set_err("bases_id %llu not cached and bases is NULL",
-                        (unsigned long long)bases_id);
-                return -4;
-            }
-            CachedBases cb;
-            cb.n = n;
-            HIP_TRY(hipMalloc(&cb.d_ptr, n * sizeof(g1_affine)));
-            int rc = staged_upload(ds, cb.d_ptr, bases, n * 64);
-            if (rc) return rc;
-            ds.bases_cache.emplace(key, cb);
-            d_b = cb.d_ptr;
-        }
-    } else {
-        if (!bases) {
-            set_err("bases is NULL");
-            return -1;
-        }
-        if (ds.base_cap < n) {
-            if (ds.d_bases) (void)hipFree(ds.d_bases);
-            HIP_TRY(hipMalloc(&ds.d_bases, n * sizeof(g1_affine)));
-            ds.base_cap = n;
-        }
-        int rc = staged_upload(ds, ds.d_bases, bases, n * 64);
-        if (rc) return rc;
-        d_b = ds.d_bases;
-    }
-    return spectre_gpu_msm_g1_batch_device(ctx, 0, d_b, ds.d_scalars, nbatch,
-                                           n, flags, out_affine);
+    RC_TRY(upload_scalars(ds, scalars, (size_t)nbatch * n * 32));
+    const g1_affine* d_b = nullptr;
+    RC_TRY(resolve_bases(ds, bases_id, 1, n, bases, n, &d_b));
+    return spectre_gpu_msm_g1_batch_device(ctx, 0, d_b, ds.d_scalars.ptr,
+                                           nbatch, n, flags, out_affine);
 }
 
 // upload + enqueue one device's shard of an n-point MSM split num_gpus ways
@@ -458,57 +419,13 @@ static int msm_multi_enqueue_one(spectre_gpu_ctx* ctx, int d, int num_gpus,
     HIP_TRY(hipSetDevice(ds.device_id));
     const uint64_t lo = n * d / num_gpus, hi = n * (d + 1) / num_gpus;
     const uint64_t m = hi - lo;
-    // scalars: plain scratch upload
-    if (ds.scal_cap < m * 32) {
-        if (ds.d_scalars) { (void)hipFree(ds.d_scalars); ds.d_scalars = nullptr; }
-        ds.scal_cap = 0;
-        HIP_TRY(hipMalloc(&ds.d_scalars, m * 32));
-        ds.scal_cap = m * 32;
-    }
-    {
-        int rc = staged_upload(ds, ds.d_scalars, scalars + lo * 32, m * 32);
-        if (rc) return rc;
-    }
-    // bases: cached per (bases_id, n, num_gpus) — this device's chunk layout
-    // depends on all three, so all three form the cache key.
-    g1_affine* d_b = nullptr;
-    if (bases_id != 0) {
-        std::array<uint64_t, 3> key{bases_id, n, (uint64_t)num_gpus};
-        auto it = ds.bases_cache.find(key);
-        if (it != ds.bases_cache.end()) {
-            d_b = it->second.d_ptr;
-        } else {
-            if (!bases) {
-                set_err("bases_id %llu not cached and bases is NULL",
-                        (unsigned long long)bases_id);
-                return -4;
-            }
-            CachedBases cb;
-            cb.n = m;
-            HIP_TRY(hipMalloc(&cb.d_ptr, m * sizeof(g1_affine)));
-            int rc = staged_upload(ds, cb.d_ptr, bases + lo * 64, m * 64);
-            if (rc) return rc;
-            ds.bases_cache.emplace(key, cb);
-            d_b = cb.d_ptr;
-        }
-    } else {
-        if (!bases) {
-            set_err("bases is NULL");
-            return -1;
-        }
-        if (ds.base_cap < m) {
-            if (ds.d_bases) { (void)hipFree(ds.d_bases); ds.d_bases = nullptr; }
-            ds.base_cap = 0;
-            HIP_TRY(hipMalloc(&ds.d_bases, m * sizeof(g1_affine)));
-            ds.base_cap = m;
-        }
-        int rc = staged_upload(ds, ds.d_bases, bases + lo * 64, m * 64);
-        if (rc) return rc;
-        d_b = ds.d_bases;
-    }
+    RC_TRY(upload_scalars(ds, scalars + lo * 32, m * 32));
+    const g1_affine* d_b = nullptr;
+    RC_TRY(resolve_bases(ds, bases_id, (uint64_t)num_gpus, n,
+                         bases ? bases + lo * 64 : nullptr, m, &d_b));
     // enqueue without synchronizing so all shards run concurrently
-    return msm_batch_shard_device(ctx, d, d_b, ds.d_scalars, 1, m, flags,
-                                  wins_out, nullptr, /*sync=*/false);
+    return msm_device(ctx, d, msm_call(d_b, ds.d_scalars.ptr, 1, m, flags),
+                      wins_out, nullptr, /*sync=*/false, 0);
 }
 
 int spectre_gpu_msm_g1(spectre_gpu_ctx* ctx, uint64_t bases_id,
@@ -538,19 +455,16 @@ int spectre_gpu_msm_g1(spectre_gpu_ctx* ctx, uint64_t bases_id,
                                        scalars, n, flags,
                                        &wins[(size_t)d * MSM_NWIN]);
         if (rc) {
-            // Devices <= d may have kernels and an async D2H into `wins`
-            // in flight; drain them before the vector goes out of scope.
-            for (int e = 0; e <= d; e++) {
-                (void)hipSetDevice(ctx->devs[e].device_id);
-                (void)hipStreamSynchronize(ctx->devs[e].stream);
-            }
+            // Devices <= d may have kernels and a pending hand-off into
+            // `wins` in flight; drain them while the vector is alive. The
+            // first error is the one reported.
+            const std::string first = g_last_error;
+            for (int e = 0; e <= d; e++) (void)msm_slot_drain(ctx, e, 0);
+            g_last_error = first;
             return rc;
         }
     }
-    for (int d = 0; d < num_gpus; d++) {
-        int rc = msm_slot_drain(ctx, d, 0);
-        if (rc) return rc;
-    }
+    for (int d = 0; d < num_gpus; d++) RC_TRY(msm_slot_drain(ctx, d, 0));
     return spectre_gpu_msm_g1_combine((const uint8_t*)wins.data(),
                                       (uint32_t)num_gpus, out_affine);
 }
@@ -582,18 +496,11 @@ int spectre_gpu_ntt_fr(spectre_gpu_ctx* ctx, uint8_t* data, uint32_t log_n,
     const uint64_t n = 1ull << log_n;
     // cached IO buffer: the Rust seam calls this entry ~40-60x per proof and
     // must not pay a (up to 1 GB) hipMalloc/hipFree per transform.
-    if (ds.ntt_io_cap < n) {
-        if (ds.d_ntt_io) { (void)hipFree(ds.d_ntt_io); ds.d_ntt_io = nullptr; }
-        ds.ntt_io_cap = 0;
-        HIP_TRY(hipMalloc(&ds.d_ntt_io, n * 32));
-        ds.ntt_io_cap = n;
-    }
-    int rc = staged_upload(ds, ds.d_ntt_io, data, n * 32);
-    if (rc == 0)
-        rc = spectre_gpu_ntt_fr_device(ctx, 0, ds.d_ntt_io, log_n, omega,
-                                       inverse, coset_gen);
-    if (rc == 0) rc = staged_download(ds, data, ds.d_ntt_io, n * 32);
-    return rc;
+    RC_TRY(ds.d_ntt_io.reserve(n));
+    RC_TRY(staged_upload(ds, ds.d_ntt_io.ptr, data, n * 32));
+    RC_TRY(spectre_gpu_ntt_fr_device(ctx, 0, ds.d_ntt_io.ptr, log_n, omega,
+                                     inverse, coset_gen));
+    return staged_download(ds, data, ds.d_ntt_io.ptr, n * 32);
 }
 
 int spectre_gpu_fr_gate_eval(spectre_gpu_ctx* ctx, int dev,

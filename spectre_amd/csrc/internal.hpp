@@ -21,9 +21,6 @@
 #define MSM_WBITS 16
 #define MSM_NWIN 16                        // ceil(255 / WBITS)
 #define MSM_BPW (1u << (MSM_WBITS - 1))    // buckets per window
-#define MSM_NB_TOTAL (MSM_NWIN * MSM_BPW)
-#define MSM_SKIP_KEY MSM_NB_TOTAL          // sorts after all real keys
-#define MSM_SORT_BITS 20                   // key range < 2^20
 #ifndef MSM_CHUNK
 #define MSM_CHUNK 8                        // buckets per reduction thread
 #endif
@@ -33,91 +30,6 @@
 #define MSM_ACC_E_MIN 8
 #define MSM_ACC_E_MAX 64
 #define MSM_ACC_TARGET_BLOCKS 2            // accumulate blocks aimed at per CU
-
-struct NttPlan {
-    fp256* tw1 = nullptr;  // butterfly twiddles, axis 1
-    fp256* tw2 = nullptr;  // butterfly twiddles, axis 2
-    fp256* tw3 = nullptr;  // butterfly twiddles, axis 3 (3-pass only)
-    fp256* twB = nullptr;  // T1 || T2 omega-power lookup (w^e = T1[e&fff]*T2[e>>12])
-    uint32_t k1 = 0, k2 = 0, k3 = 0;
-};
-
-struct CachedBases {
-    g1_affine* d_ptr = nullptr;
-    uint64_t n = 0;
-};
-
-// Per-slot MSM pipeline state: two slots per device let call i+1's
-// digits/sort/accumulate fill the machine while call i's latency-bound
-// reduction tail (~1.3 ms at <=1 wave/SIMD) drains on the other stream —
-// back-to-back commits (create_proof issues ~45 per proof) overlap instead
-// of serializing on the tail.
-struct MsmSlot {
-    hipStream_t stream = nullptr;  // slot 0 aliases DeviceState::stream
-    uint32_t* d_keys_in = nullptr;
-    uint32_t* d_keys_out = nullptr;
-    uint32_t* d_vals_in = nullptr;
-    uint32_t* d_vals_out = nullptr;
-    size_t ent_cap = 0;  // capacity in entries (16*n)
-    void* d_sort_tmp = nullptr;
-    size_t sort_tmp_cap = 0;
-    size_t nb_cap = 0;              // bucket-array capacity (batched)
-    uint32_t* d_offsets = nullptr;  // nb_cap + 1
-    g1_jac* d_buckets = nullptr;    // MSM_NB_TOTAL
-    uint32_t* d_firstK = nullptr;   // boundary-run side arrays (side_cap)
-    uint32_t* d_lastK = nullptr;
-    g1_jac* d_firstP = nullptr;
-    g1_jac* d_lastP = nullptr;
-    size_t side_cap = 0;            // capacity in accumulate threads
-    g1_jac* d_red = nullptr;        // reduction ping-pong (NB_TOTAL/CHUNK * 2)
-    // Window sums come back through a PINNED per-slot buffer: an async D2H
-    // into caller (pageable) memory silently blocks the calling thread on
-    // ROCm, which serialized the whole two-slot pipeline in r2's first
-    // measurement. The wait/drain step memcpys pinned -> caller.
-    g1_jac* h_wins = nullptr;   // pinned, h_wins_cap elements
-    size_t h_wins_cap = 0;
-    g1_jac* pending_dst = nullptr;  // caller buffer for the in-flight call
-    uint32_t pending_n = 0;         // elements pending (nbatch * NWIN)
-};
-
-struct DeviceState {
-    int device_id = 0;
-    hipStream_t stream = nullptr;
-    MsmSlot slots[3];  // >=2 enables the async pipeline; 3rd for depth-3 A/B
-    int next_slot = 0;  // round-robin for the async API
-    int num_cus = 0;              // filled with acc_resident_blocks
-    int acc_resident_blocks = 0;  // k_bucket_acc blocks resident per CU
-    uint8_t* d_scalars = nullptr;
-    size_t scal_cap = 0;  // bytes
-    g1_affine* d_bases = nullptr;
-    size_t base_cap = 0;  // points
-    // key = (bases_id, n, shard layout): layout is num_gpus for the sharded
-    // path (this device's contiguous chunk of an n-point set split num_gpus
-    // ways) and 1 for the full set (batch path == num_gpus=1 shard).
-    std::map<std::array<uint64_t, 3>, CachedBases> bases_cache;
-    // ---- pinned staging for host-pointer uploads/downloads ----
-    uint8_t* h_stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    // ---- NTT scratch ----
-    fp256* d_ntt_tmp = nullptr;
-    size_t ntt_cap = 0;  // elements
-    fp256* d_ntt_io = nullptr;  // cached device buffer for host-pointer NTTs
-    size_t ntt_io_cap = 0;      // elements (the Rust seam calls this path
-                                // ~40-60x per proof; no per-call hipMalloc)
-    fp256* d_cosetA = nullptr;  // coset base tables (n2 resp. n1 entries)
-    fp256* d_cosetB = nullptr;
-    size_t coset_cap = 0;
-    // ---- gate-eval scratch (program, constants, column-pointer array) ----
-    uint8_t* d_gate = nullptr;
-    size_t gate_cap = 0;  // bytes
-    std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n||inverse
-};
-
-struct spectre_gpu_ctx {
-    std::vector<DeviceState> devs;
-    std::recursive_mutex mu;
-    uint32_t msm_acc_entries = 0;  // entries per accumulate thread, 0 = auto
-};
 
 void set_err(const char* fmt, ...);
 
@@ -131,38 +43,168 @@ void set_err(const char* fmt, ...);
         }                                                                 \
     } while (0)
 
-// msm.hip — runs the full Pippenger pipeline for one shard on device `dev`'s
-// stream and writes the MSM_NWIN Jacobian window sums to host memory
-// (synchronizes the stream). If stage_ms != nullptr, per-stage HIP-event
-// timings are written: [0]=digits [1]=sort [2]=offsets [3]=bucket_acc
-// [4]=chunks [5]=reduce [6]=total-gpu [7]=real (non-zero-digit) entry count.
-int msm_shard_device(spectre_gpu_ctx* ctx, int dev, const g1_affine* d_bases,
-                     const uint8_t* d_scalars, uint64_t n, uint32_t flags,
-                     g1_jac* winsums_host, double* stage_ms = nullptr);
-// batch variant: nbatch scalar vectors (batch-major, nbatch*n*32 B) over one
-// shared base set; winsums_host receives nbatch*MSM_NWIN Jacobian sums.
-// sync=false: enqueue the pipeline + async D2H of winsums on the slot's
-// stream and return without synchronizing (multi-device / pipelined
-// overlap; the caller must hipStreamSynchronize that stream before reading
-// winsums_host). slot selects the per-device pipeline slot (scratch +
-// stream); slot 1's stream is created lazily.
-int msm_batch_shard_device(spectre_gpu_ctx* ctx, int dev,
-                           const g1_affine* d_bases, const uint8_t* d_scalars,
-                           uint32_t nbatch, uint64_t n, uint32_t flags,
-                           g1_jac* winsums_host, double* stage_ms = nullptr,
-                           bool sync = true, int slot = 0);
+// propagate a nonzero return code
+#define RC_TRY(x)                                                         \
+    do {                                                                  \
+        int _rc = (x);                                                    \
+        if (_rc) return _rc;                                              \
+    } while (0)
 
-// msm.hip — window-ranged pipeline: only windows [w_lo, w_lo+w_cnt) are
-// decomposed/accumulated (window-sharded multi-GPU: bucket work AND the
-// reduction tail divide by the shard count; the carry recoding still runs
-// over all windows). winsums_host receives nbatch * w_cnt Jacobian sums.
-int msm_batch_windows_device(spectre_gpu_ctx* ctx, int dev,
-                             const g1_affine* d_bases,
-                             const uint8_t* d_scalars, uint32_t nbatch,
-                             uint64_t n, uint32_t flags, uint32_t w_lo,
-                             uint32_t w_cnt, g1_jac* winsums_host,
-                             double* stage_ms = nullptr, bool sync = true,
-                             int slot = 0);
+// Growable scratch: a pointer and its capacity in elements, in device memory
+// or (kPinned) pinned host memory. Growth frees first and never preserves
+// contents; the pointer is null and the capacity 0 until an allocation has
+// succeeded, so a failed reserve() leaves nothing dangling. Plain data on
+// purpose (DeviceState is copied into ctx->devs); owners call release()
+// with the right device current.
+template <typename T, bool kPinned = false>
+struct DevBuf {
+    T* ptr = nullptr;
+    size_t cap = 0;  // elements
+    int reserve(size_t n) {
+        if (cap >= n) return 0;
+        release();
+        void* p = nullptr;
+        if (kPinned) HIP_TRY(hipHostMalloc(&p, n * sizeof(T)));
+        else HIP_TRY(hipMalloc(&p, n * sizeof(T)));
+        ptr = (T*)p;
+        cap = n;
+        return 0;
+    }
+    void release() {
+        if (ptr) (void)(kPinned ? hipHostFree(ptr) : hipFree(ptr));
+        ptr = nullptr;
+        cap = 0;
+    }
+};
+template <typename T>
+using PinnedBuf = DevBuf<T, true>;
+template <typename... B>
+void release_all(B&... b) {
+    (b.release(), ...);
+}
+
+struct NttPlan {
+    DevBuf<fp256> tw1;  // butterfly twiddles, axis 1
+    DevBuf<fp256> tw2;  // butterfly twiddles, axis 2
+    DevBuf<fp256> tw3;  // butterfly twiddles, axis 3 (3-pass only)
+    DevBuf<fp256> twB;  // T1 || T2 omega-power lookup (w^e = T1[e&fff]*T2[e>>12])
+    uint32_t k1 = 0, k2 = 0, k3 = 0;
+    void release() { release_all(tw1, tw2, tw3, twB); }
+};
+
+// Per-slot MSM pipeline state: MSM_SLOTS slots per device let call i+1's
+// digits/sort/accumulate fill the machine while call i's latency-bound
+// reduction tail (~1.3 ms at <=1 wave/SIMD) drains on another stream —
+// back-to-back commits (create_proof issues ~45 per proof) overlap instead
+// of serializing on the tail. Sizes below are per call: ent = nbatch *
+// w_cnt * n sort entries, nbt = nbatch * w_cnt * MSM_BPW buckets.
+#define MSM_SLOTS 3  // >=2 enables the async pipeline; 3rd for depth-3 A/B
+struct MsmSlot {
+    hipStream_t stream = nullptr;  // slot 0 aliases DeviceState::stream
+    // sort keys/values, ent rounded up to whole quads; grow together
+    DevBuf<uint32_t> d_keys_in, d_keys_out, d_vals_in, d_vals_out;
+    DevBuf<uint8_t> d_sort_tmp;  // radix-sort temp storage (bytes)
+    // boundary-run side arrays, one entry per accumulate thread
+    // (ceil(ent / entries-per-thread)); grow together
+    DevBuf<uint32_t> d_firstK, d_lastK;
+    DevBuf<g1_jac> d_firstP, d_lastP;
+    // grow together:
+    DevBuf<uint32_t> d_offsets;  // nbt + 1 segment bounds
+    DevBuf<g1_jac> d_buckets;    // nbt
+    DevBuf<g1_jac> d_red;        // nbt/MSM_CHUNK chunk sums, then the
+                                 // nbatch * w_cnt window sums
+    // Window sums come back through a PINNED per-slot buffer: an async D2H
+    // into caller (pageable) memory silently blocks the calling thread on
+    // ROCm, which serialized the whole slot pipeline in r2's first
+    // measurement. msm_slot_drain memcpys pinned -> caller.
+    PinnedBuf<g1_jac> h_wins;
+    // Result hand-off, set by the enqueue and cleared by msm_slot_drain
+    // (msm.hip) and nowhere else; non-null = the slot is busy.
+    g1_jac* pending_dst = nullptr;  // caller buffer for the in-flight call
+    uint32_t pending_n = 0;         // elements pending (nbatch * w_cnt)
+    void release(hipStream_t shared) {
+        release_all(d_keys_in, d_keys_out, d_vals_in, d_vals_out, d_sort_tmp,
+                    d_firstK, d_lastK, d_firstP, d_lastP, d_offsets,
+                    d_buckets, d_red, h_wins);
+        if (stream && stream != shared) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+};
+
+struct DeviceState {
+    int device_id = 0;
+    hipStream_t stream = nullptr;
+    MsmSlot slots[MSM_SLOTS];
+    int next_slot = 0;  // round-robin for the async API
+    int num_cus = 0;              // filled with acc_resident_blocks
+    int acc_resident_blocks = 0;  // k_bucket_acc blocks resident per CU
+    DevBuf<uint8_t> d_scalars;   // host-pointer MSM scratch (bytes)
+    DevBuf<g1_affine> d_bases;   // uncached host-pointer bases (points)
+    // key = (bases_id, n, shard layout): layout is num_gpus for the sharded
+    // path (this device's contiguous chunk of an n-point set split num_gpus
+    // ways) and 1 for the full set (batch path == num_gpus=1 shard).
+    std::map<std::array<uint64_t, 3>, DevBuf<g1_affine>> bases_cache;
+    // ---- pinned staging for host-pointer uploads/downloads ----
+    PinnedBuf<uint8_t> h_stage[2];
+    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    // ---- NTT scratch (elements) ----
+    DevBuf<fp256> d_ntt_tmp;
+    DevBuf<fp256> d_ntt_io;   // cached device buffer for host-pointer NTTs
+                              // (the Rust seam calls this path ~40-60x per
+                              // proof; no per-call hipMalloc)
+    DevBuf<fp256> d_cosetA;   // coset power tables T1 || T2
+    // ---- gate-eval scratch (column pointers, constants, program; bytes) ----
+    DevBuf<uint8_t> d_gate;
+    std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n||inverse
+    // frees everything this device owns; the caller has made it current
+    void release() {
+        for (auto& sl : slots) sl.release(stream);
+        release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
+                    d_ntt_io, d_cosetA, d_gate);
+        for (auto& kv : bases_cache) kv.second.release();
+        bases_cache.clear();
+        for (auto& kv : plans) kv.second.release();
+        plans.clear();
+        for (auto& e : stage_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+};
+
+struct spectre_gpu_ctx {
+    std::vector<DeviceState> devs;
+    std::recursive_mutex mu;
+    uint32_t msm_acc_entries = 0;  // entries per accumulate thread, 0 = auto
+};
+
+// One MSM pipeline run: nbatch scalar vectors (batch-major, nbatch*n*32 B)
+// over one shared base set, restricted to windows [w_lo, w_lo+w_cnt).
+// Full-range callers pass 0, MSM_NWIN. In a window shard the bucket work AND
+// the reduction tail divide by the shard count; the carry recoding still
+// runs over all windows.
+struct MsmCall {
+    const g1_affine* d_bases;
+    const uint8_t* d_scalars;
+    uint32_t nbatch;
+    uint64_t n;
+    uint32_t flags;
+    uint32_t w_lo, w_cnt;
+};
+
+// msm.hip — the one MSM device entry point: runs the Pippenger pipeline for
+// `call` on pipeline slot `slot` (scratch + stream; streams of slots > 0 are
+// created lazily) of device `dev`; winsums_host receives nbatch * w_cnt
+// Jacobian window sums. A slot with a result pending rejects every call.
+// sync=false: enqueue the pipeline and the D2H of the sums and return; the
+// sums are delivered by msm_slot_drain (multi-device / pipelined overlap).
+// stage_ms != nullptr (always synchronizes): per-stage HIP-event timings
+// [0]=digits [1]=sort [2]=offsets [3]=bucket_acc [4]=chunks [5]=reduce
+// [6]=total-gpu [7]=real (non-zero-digit) entry count.
+int msm_device(spectre_gpu_ctx* ctx, int dev, const MsmCall& call,
+               g1_jac* winsums_host, double* stage_ms, bool sync, int slot);
 
 // msm.hip — the auto rule for entries per accumulate thread (pure; host).
 uint32_t msm_acc_auto_entries(uint64_t entries, uint32_t cus,

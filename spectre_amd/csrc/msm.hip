@@ -396,62 +396,31 @@ static int ensure_acc_geometry(DeviceState& dstate) {
     return 0;
 }
 
-static int ensure_msm_scratch(MsmSlot& ds, hipStream_t stream, uint64_t n,
-                              uint32_t nbatch, uint32_t w_cnt,
+static int ensure_msm_scratch(MsmSlot& ds, uint64_t ent, uint32_t nwin,
                               uint32_t acc_e) {
-    const uint64_t ent = (uint64_t)nbatch * w_cnt * n;
-    const uint64_t nbt = (uint64_t)nbatch * w_cnt * MSM_BPW;
-    if (ds.ent_cap < ent) {
-        // free-and-null before reallocating: a failed hipMalloc below must
-        // not leave dangling pointers with a stale capacity (the caps are
-        // only advanced after every allocation in the group succeeds).
-        ds.ent_cap = 0;
-        for (void** p : {(void**)&ds.d_keys_in, (void**)&ds.d_keys_out,
-                         (void**)&ds.d_vals_in, (void**)&ds.d_vals_out})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        // whole quads: k_bucket_acc reads keys/values 16 bytes at a time
-        const uint64_t ent4 = (ent + 3) & ~3ull;
-        HIP_TRY(hipMalloc(&ds.d_keys_in, ent4 * 4));
-        HIP_TRY(hipMalloc(&ds.d_keys_out, ent4 * 4));
-        HIP_TRY(hipMalloc(&ds.d_vals_in, ent4 * 4));
-        HIP_TRY(hipMalloc(&ds.d_vals_out, ent4 * 4));
-        ds.ent_cap = ent;
-    }
+    const uint64_t nbt = (uint64_t)nwin * MSM_BPW;
+    // Each group is reserved with one size, so its members grow together; a
+    // group left half-grown by a failed allocation is finished by the next
+    // call (every buffer carries its own capacity).
+    // whole quads: k_bucket_acc reads keys/values 16 bytes at a time
+    const uint64_t ent4 = (ent + 3) & ~3ull;
+    for (auto* b : {&ds.d_keys_in, &ds.d_keys_out, &ds.d_vals_in,
+                    &ds.d_vals_out})
+        RC_TRY(b->reserve(ent4));
     // boundary-run side arrays: one slot per accumulate thread of THIS call
     const uint64_t nt = (ent + acc_e - 1) / acc_e;
-    if (ds.side_cap < nt) {
-        ds.side_cap = 0;
-        for (void** p : {(void**)&ds.d_firstK, (void**)&ds.d_lastK,
-                         (void**)&ds.d_firstP, (void**)&ds.d_lastP})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        HIP_TRY(hipMalloc(&ds.d_firstK, nt * 4));
-        HIP_TRY(hipMalloc(&ds.d_lastK, nt * 4));
-        HIP_TRY(hipMalloc(&ds.d_firstP, nt * sizeof(g1_jac)));
-        HIP_TRY(hipMalloc(&ds.d_lastP, nt * sizeof(g1_jac)));
-        ds.side_cap = nt;
-    }
-    if (ds.nb_cap < nbt) {
-        ds.nb_cap = 0;
-        for (void** p : {(void**)&ds.d_offsets, (void**)&ds.d_buckets,
-                         (void**)&ds.d_red})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        HIP_TRY(hipMalloc(&ds.d_offsets, (nbt + 1) * 4));
-        HIP_TRY(hipMalloc(&ds.d_buckets, nbt * sizeof(g1_jac)));
-        HIP_TRY(hipMalloc(&ds.d_red,
-                          (nbt / MSM_CHUNK + nbatch * w_cnt) * sizeof(g1_jac)));
-        ds.nb_cap = nbt;
-    }
+    RC_TRY(ds.d_firstK.reserve(nt));
+    RC_TRY(ds.d_lastK.reserve(nt));
+    RC_TRY(ds.d_firstP.reserve(nt));
+    RC_TRY(ds.d_lastP.reserve(nt));
+    RC_TRY(ds.d_offsets.reserve(nbt + 1));
+    RC_TRY(ds.d_buckets.reserve(nbt));
+    RC_TRY(ds.d_red.reserve(nbt / MSM_CHUNK + nwin));
     size_t sort_need = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_need, ds.d_keys_in,
-                                             ds.d_keys_out, ds.d_vals_in,
-                                             ds.d_vals_out, (int64_t)ent, 0,
-                                             32, stream);
-    if (ds.sort_tmp_cap < sort_need) {
-        if (ds.d_sort_tmp) (void)hipFree(ds.d_sort_tmp);
-        HIP_TRY(hipMalloc(&ds.d_sort_tmp, sort_need));
-        ds.sort_tmp_cap = sort_need;
-    }
-    return 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(
+        nullptr, sort_need, ds.d_keys_in.ptr, ds.d_keys_out.ptr,
+        ds.d_vals_in.ptr, ds.d_vals_out.ptr, (int64_t)ent, 0, 32, ds.stream);
+    return ds.d_sort_tmp.reserve(sort_need);
 }
 
 static int end_bit_for(uint64_t max_key) {
@@ -460,150 +429,30 @@ static int end_bit_for(uint64_t max_key) {
     return b;
 }
 
-int msm_batch_shard_device(spectre_gpu_ctx* ctx, int dev,
-                           const g1_affine* d_bases, const uint8_t* d_scalars,
-                           uint32_t nbatch, uint64_t n, uint32_t flags,
-                           g1_jac* winsums_host, double* stage_ms, bool sync,
-                           int slot) {
-    return msm_batch_windows_device(ctx, dev, d_bases, d_scalars, nbatch, n,
-                                    flags, 0, MSM_NWIN, winsums_host,
-                                    stage_ms, sync, slot);
-}
-
-// window-ranged pipeline: nwin = w_cnt windows starting at w_lo; winsums_host
-// receives nbatch * w_cnt Jacobian sums (full-range callers pass 0, NWIN).
-int msm_batch_windows_device(spectre_gpu_ctx* ctx, int dev,
-                             const g1_affine* d_bases,
-                             const uint8_t* d_scalars, uint32_t nbatch,
-                             uint64_t n, uint32_t flags, uint32_t w_lo,
-                             uint32_t w_cnt, g1_jac* winsums_host,
-                             double* stage_ms, bool sync, int slot) {
-    DeviceState& dstate = ctx->devs[dev];
-    HIP_TRY(hipSetDevice(dstate.device_id));
-    if (slot < 0 || slot > 2) {
-        set_err("msm: slot %d out of range", slot);
-        return -3;
+// Per-stage HIP events on the slot's stream (the live in-bench measurement
+// the roofline report is built from). Events exist only when timing was
+// asked for and are destroyed on every return path.
+struct StageTimer {
+    hipEvent_t ev[7] = {};
+    hipStream_t st = nullptr;
+    hipError_t err = hipSuccess;  // first failed record, reported by read()
+    uint32_t ent_real = 0;        // non-zero-digit entries (off[nbt])
+    bool on = false;
+    ~StageTimer() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
     }
-    MsmSlot& ds = dstate.slots[slot];
-    if (!sync && ds.pending_dst) {
-        // a second in-flight call on one slot would overwrite the pending
-        // D2H silently — fail loudly instead (callers must slot_wait first)
-        set_err("msm: slot %d already has a call in flight", slot);
-        return -3;
-    }
-    if (!ds.stream) {
-        if (slot == 0) ds.stream = dstate.stream;
-        else HIP_TRY(hipStreamCreate(&ds.stream));
-    }
-    if (nbatch == 0 || nbatch > SPECTRE_MSM_MAX_BATCH) {
-        set_err("msm: nbatch %u out of range [1,%d]", nbatch,
-                SPECTRE_MSM_MAX_BATCH);
-        return -3;
-    }
-    // Sort entries and segment offsets are indexed with uint32: at exactly
-    // nbatch*NWIN*n == 2^32 the final offset off[nb_total] wraps to 0 and the
-    // result is silently wrong. Reject; callers split such jobs (e.g. batch
-    // 32 x 2^23 -> 2 x 16).
-
-    if (w_lo >= MSM_NWIN || w_cnt == 0 || w_lo + w_cnt > MSM_NWIN) {
-        set_err("msm: window range [%u, %u+%u) out of [0,%d)", w_lo, w_lo,
-                w_cnt, MSM_NWIN);
-        return -3;
-    }
-    if ((uint64_t)nbatch * w_cnt * n >= (1ull << 32)) {
-        set_err("msm: nbatch*%u*n = %llu exceeds 2^32 sort-entry limit "
-                "(split the batch or shard the MSM)",
-                w_cnt, (unsigned long long)((uint64_t)nbatch * w_cnt * n));
-        return -3;
-    }
-    if (n == 0) {
-        for (uint32_t w = 0; w < nbatch * w_cnt; w++)
-            g1j_set_inf(winsums_host[w]);
-        return 0;
-    }
-    const uint64_t ent = (uint64_t)nbatch * w_cnt * n;
-    int rc = ensure_acc_geometry(dstate);
-    if (rc) return rc;
-    const uint32_t acc_e =
-        ctx->msm_acc_entries
-            ? ctx->msm_acc_entries
-            : msm_acc_auto_entries(ent, (uint32_t)dstate.num_cus,
-                                   (uint32_t)dstate.acc_resident_blocks);
-    rc = ensure_msm_scratch(ds, ds.stream, n, nbatch, w_cnt, acc_e);
-    if (rc) return rc;
-    const uint32_t nbt = nbatch * w_cnt * MSM_BPW;
-    const int canonical = (flags & SPECTRE_SCALARS_CANONICAL) ? 1 : 0;
-    hipStream_t st = ds.stream;
-
-    // optional per-stage HIP events (on the library stream — this is the
-    // live in-bench measurement the roofline report is built from)
-    hipEvent_t ev[7];
-    if (stage_ms)
+    int start(hipStream_t s) {
+        on = true;
+        st = s;
         for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-#define STAMP(i) \
-    if (stage_ms) HIP_TRY(hipEventRecord(ev[i], st));
-
-    STAMP(0);
-    uint32_t blocks = (uint32_t)((n + THREADS - 1) / THREADS);
-    hipLaunchKernelGGL(k_msm_digits, dim3(blocks), dim3(THREADS), 0, st,
-                       d_scalars, n, nbatch, canonical, w_lo, w_cnt,
-                       ds.d_keys_in, ds.d_vals_in);
-    STAMP(1);
-    size_t tmp = ds.sort_tmp_cap;
-    (void)hipcub::DeviceRadixSort::SortPairs(
-        ds.d_sort_tmp, tmp, ds.d_keys_in, ds.d_keys_out, ds.d_vals_in,
-        ds.d_vals_out, (int64_t)ent, 0, end_bit_for(nbt), st);
-    STAMP(2);
-    hipLaunchKernelGGL(k_bucket_offsets,
-                       dim3((nbt + 1 + THREADS - 1) / THREADS), dim3(THREADS),
-                       0, st, ds.d_keys_out, ent, nbt, ds.d_offsets);
-    STAMP(3);
-    const uint32_t nt_acc = (uint32_t)((ent + acc_e - 1) / acc_e);
-    hipLaunchKernelGGL(k_bucket_acc,
-                       dim3((nt_acc + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS),
-                       dim3(MSM_ACC_THREADS), 0, st, ds.d_offsets,
-                       ds.d_keys_out, ds.d_vals_out, d_bases, nbt, acc_e,
-                       ds.d_buckets, ds.d_firstK, ds.d_firstP, ds.d_lastK,
-                       ds.d_lastP);
-    hipLaunchKernelGGL(k_bucket_fix,
-                       dim3((nbt + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS),
-                       dim3(MSM_ACC_THREADS), 0, st, ds.d_offsets,
-                       ds.d_firstK, ds.d_firstP, ds.d_lastK, ds.d_lastP, nbt,
-                       acc_e, ds.d_buckets);
-    STAMP(4);
-    const uint32_t nchunks = nbt / MSM_CHUNK;
-    g1_jac* red0 = ds.d_red;
-    g1_jac* red1 = ds.d_red + nchunks;
-    hipLaunchKernelGGL(k_window_chunks,
-                       dim3((nchunks + THREADS - 1) / THREADS), dim3(THREADS),
-                       0, st, ds.d_buckets, nchunks, red0);
-    STAMP(5);
-    hipLaunchKernelGGL(k_window_sum, dim3(nbatch * w_cnt),
-                       dim3(WSUM_THREADS), 0, st, red0, red1);
-    STAMP(6);
-    const uint32_t nw = nbatch * w_cnt;
-    if (ds.h_wins_cap < nw) {
-        if (ds.h_wins) (void)hipHostFree(ds.h_wins);
-        ds.h_wins_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&ds.h_wins, (size_t)nw * sizeof(g1_jac)));
-        ds.h_wins_cap = nw;
-    }
-    HIP_TRY(hipMemcpyAsync(ds.h_wins, red1, (size_t)nw * sizeof(g1_jac),
-                           hipMemcpyDeviceToHost, st));
-    uint32_t ent_real = 0;
-    if (stage_ms)
-        HIP_TRY(hipMemcpyAsync(&ent_real, ds.d_offsets + nbt, 4,
-                               hipMemcpyDeviceToHost, st));
-    if (!sync && !stage_ms) {
-        HIP_TRY(hipGetLastError());
-        ds.pending_dst = winsums_host;  // drained by msm_slot_drain
-        ds.pending_n = nw;
         return 0;
     }
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipGetLastError());
-    memcpy(winsums_host, ds.h_wins, (size_t)nw * sizeof(g1_jac));
-    if (stage_ms) {
+    void stamp(int i) {
+        if (on && err == hipSuccess) err = hipEventRecord(ev[i], st);
+    }
+    int read(double* stage_ms) {  // after the stream has been synchronized
+        HIP_TRY(err);
         float ms;
         for (int i = 0; i < 6; i++) {
             HIP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
@@ -612,35 +461,160 @@ int msm_batch_windows_device(spectre_gpu_ctx* ctx, int dev,
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[6]));
         stage_ms[6] = ms;
         stage_ms[7] = (double)ent_real;
-        for (auto& e : ev) (void)hipEventDestroy(e);
+        return 0;
     }
-#undef STAMP
+};
+
+// Validate the call and hand out its slot (stream created on first use).
+static int msm_acquire_slot(DeviceState& dstate, const MsmCall& c, int slot,
+                            MsmSlot** out) {
+    HIP_TRY(hipSetDevice(dstate.device_id));
+    if (slot < 0 || slot >= MSM_SLOTS) {
+        set_err("msm: slot %d out of range", slot);
+        return -3;
+    }
+    MsmSlot& ds = dstate.slots[slot];
+    if (ds.pending_dst) {
+        // a second call on a busy slot, synchronous or not, would overwrite
+        // the pinned window sums of the pending one silently — fail loudly
+        // instead (callers must slot_wait first)
+        set_err("msm: slot %d already has a call in flight", slot);
+        return -3;
+    }
+    if (!ds.stream) {
+        if (slot == 0) ds.stream = dstate.stream;
+        else HIP_TRY(hipStreamCreate(&ds.stream));
+    }
+    if (c.nbatch == 0 || c.nbatch > SPECTRE_MSM_MAX_BATCH) {
+        set_err("msm: nbatch %u out of range [1,%d]", c.nbatch,
+                SPECTRE_MSM_MAX_BATCH);
+        return -3;
+    }
+    if (c.w_lo >= MSM_NWIN || c.w_cnt == 0 || c.w_lo + c.w_cnt > MSM_NWIN) {
+        set_err("msm: window range [%u, %u+%u) out of [0,%d)", c.w_lo, c.w_lo,
+                c.w_cnt, MSM_NWIN);
+        return -3;
+    }
+    // Sort entries and segment offsets are indexed with uint32: at exactly
+    // nbatch*NWIN*n == 2^32 the final offset off[nb_total] wraps to 0 and the
+    // result is silently wrong. Reject; callers split such jobs (e.g. batch
+    // 32 x 2^23 -> 2 x 16).
+    if ((uint64_t)c.nbatch * c.w_cnt * c.n >= (1ull << 32)) {
+        set_err("msm: nbatch*%u*n = %llu exceeds 2^32 sort-entry limit "
+                "(split the batch or shard the MSM)", c.w_cnt,
+                (unsigned long long)((uint64_t)c.nbatch * c.w_cnt * c.n));
+        return -3;
+    }
+    *out = &ds;
     return 0;
 }
 
-int msm_shard_device(spectre_gpu_ctx* ctx, int dev, const g1_affine* d_bases,
-                     const uint8_t* d_scalars, uint64_t n, uint32_t flags,
-                     g1_jac* winsums_host, double* stage_ms) {
-    return msm_batch_shard_device(ctx, dev, d_bases, d_scalars, 1, n, flags,
-                                  winsums_host, stage_ms);
+// Size the slot's scratch, launch the six stages and the D2H of the window
+// sums into the slot's pinned buffer, and mark the slot busy: msm_slot_drain
+// delivers the sums to winsums_host.
+static int msm_enqueue(spectre_gpu_ctx* ctx, DeviceState& dstate, MsmSlot& ds,
+                       const MsmCall& c, g1_jac* winsums_host,
+                       StageTimer& timer) {
+    const uint32_t nw = c.nbatch * c.w_cnt;
+    const uint64_t ent = (uint64_t)nw * c.n;
+    RC_TRY(ensure_acc_geometry(dstate));
+    const uint32_t acc_e =
+        ctx->msm_acc_entries
+            ? ctx->msm_acc_entries
+            : msm_acc_auto_entries(ent, (uint32_t)dstate.num_cus,
+                                   (uint32_t)dstate.acc_resident_blocks);
+    RC_TRY(ensure_msm_scratch(ds, ent, nw, acc_e));
+    RC_TRY(ds.h_wins.reserve(nw));
+    const uint32_t nbt = nw * MSM_BPW;
+    const int canonical = (c.flags & SPECTRE_SCALARS_CANONICAL) ? 1 : 0;
+    hipStream_t st = ds.stream;
+
+    timer.stamp(0);
+    uint32_t blocks = (uint32_t)((c.n + THREADS - 1) / THREADS);
+    hipLaunchKernelGGL(k_msm_digits, dim3(blocks), dim3(THREADS), 0, st,
+                       c.d_scalars, c.n, c.nbatch, canonical, c.w_lo, c.w_cnt,
+                       ds.d_keys_in.ptr, ds.d_vals_in.ptr);
+    timer.stamp(1);
+    size_t tmp = ds.d_sort_tmp.cap;
+    (void)hipcub::DeviceRadixSort::SortPairs(
+        ds.d_sort_tmp.ptr, tmp, ds.d_keys_in.ptr, ds.d_keys_out.ptr,
+        ds.d_vals_in.ptr, ds.d_vals_out.ptr, (int64_t)ent, 0,
+        end_bit_for(nbt), st);
+    timer.stamp(2);
+    hipLaunchKernelGGL(k_bucket_offsets,
+                       dim3((nbt + 1 + THREADS - 1) / THREADS), dim3(THREADS),
+                       0, st, ds.d_keys_out.ptr, ent, nbt, ds.d_offsets.ptr);
+    timer.stamp(3);
+    const uint32_t nt_acc = (uint32_t)((ent + acc_e - 1) / acc_e);
+    hipLaunchKernelGGL(k_bucket_acc,
+                       dim3((nt_acc + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS),
+                       dim3(MSM_ACC_THREADS), 0, st, ds.d_offsets.ptr,
+                       ds.d_keys_out.ptr, ds.d_vals_out.ptr, c.d_bases, nbt,
+                       acc_e, ds.d_buckets.ptr, ds.d_firstK.ptr,
+                       ds.d_firstP.ptr, ds.d_lastK.ptr, ds.d_lastP.ptr);
+    hipLaunchKernelGGL(k_bucket_fix,
+                       dim3((nbt + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS),
+                       dim3(MSM_ACC_THREADS), 0, st, ds.d_offsets.ptr,
+                       ds.d_firstK.ptr, ds.d_firstP.ptr, ds.d_lastK.ptr,
+                       ds.d_lastP.ptr, nbt, acc_e, ds.d_buckets.ptr);
+    timer.stamp(4);
+    const uint32_t nchunks = nbt / MSM_CHUNK;
+    g1_jac* red0 = ds.d_red.ptr;
+    g1_jac* red1 = ds.d_red.ptr + nchunks;
+    hipLaunchKernelGGL(k_window_chunks,
+                       dim3((nchunks + THREADS - 1) / THREADS), dim3(THREADS),
+                       0, st, ds.d_buckets.ptr, nchunks, red0);
+    timer.stamp(5);
+    hipLaunchKernelGGL(k_window_sum, dim3(nw), dim3(WSUM_THREADS), 0, st, red0,
+                       red1);
+    timer.stamp(6);
+    HIP_TRY(hipMemcpyAsync(ds.h_wins.ptr, red1, (size_t)nw * sizeof(g1_jac),
+                           hipMemcpyDeviceToHost, st));
+    if (timer.on)
+        HIP_TRY(hipMemcpyAsync(&timer.ent_real, ds.d_offsets.ptr + nbt, 4,
+                               hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipGetLastError());
+    ds.pending_dst = winsums_host;
+    ds.pending_n = nw;
+    return 0;
 }
 
 // Synchronize a slot's stream and deliver the pending window sums (pinned ->
-// caller memory). Idempotent when nothing is pending.
+// caller memory). Idempotent when nothing is pending. The hand-off is cleared
+// on the error returns too: a failed drain leaves neither a wedged slot nor
+// a destination that may since have been freed.
 int msm_slot_drain(spectre_gpu_ctx* ctx, int dev, int slot) {
     DeviceState& dstate = ctx->devs[dev];
-    if (slot < 0 || slot > 2) {
+    if (slot < 0 || slot >= MSM_SLOTS) {
         set_err("slot_drain: slot %d out of range", slot);
         return -1;
     }
     MsmSlot& sl = dstate.slots[slot];
+    g1_jac* const dst = sl.pending_dst;
+    const size_t bytes = (size_t)sl.pending_n * sizeof(g1_jac);
+    sl.pending_dst = nullptr;
+    sl.pending_n = 0;
     HIP_TRY(hipSetDevice(dstate.device_id));
     if (sl.stream) HIP_TRY(hipStreamSynchronize(sl.stream));
     HIP_TRY(hipGetLastError());
-    if (sl.pending_dst) {
-        memcpy(sl.pending_dst, sl.h_wins, (size_t)sl.pending_n * sizeof(g1_jac));
-        sl.pending_dst = nullptr;
-        sl.pending_n = 0;
-    }
+    if (dst) memcpy(dst, sl.h_wins.ptr, bytes);
     return 0;
+}
+
+int msm_device(spectre_gpu_ctx* ctx, int dev, const MsmCall& call,
+               g1_jac* winsums_host, double* stage_ms, bool sync, int slot) {
+    DeviceState& dstate = ctx->devs[dev];
+    MsmSlot* sl = nullptr;
+    RC_TRY(msm_acquire_slot(dstate, call, slot, &sl));
+    if (call.n == 0) {
+        for (uint32_t w = 0; w < call.nbatch * call.w_cnt; w++)
+            g1j_set_inf(winsums_host[w]);
+        return 0;
+    }
+    StageTimer timer;
+    if (stage_ms) RC_TRY(timer.start(sl->stream));
+    RC_TRY(msm_enqueue(ctx, dstate, *sl, call, winsums_host, timer));
+    if (!sync && !stage_ms) return 0;  // completed by msm_slot_drain
+    RC_TRY(msm_slot_drain(ctx, dev, slot));
+    return stage_ms ? timer.read(stage_ms) : 0;
 }

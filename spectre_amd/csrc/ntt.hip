@@ -437,18 +437,14 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
     const size_t con_b = (size_t)nconst * sizeof(fp256);
     const size_t prg_b = (size_t)nops * 12;
     const size_t need = ptr_b + con_b + prg_b;
-    if (ds.gate_cap < need) {
-        if (ds.d_gate) { (void)hipFree(ds.d_gate); ds.d_gate = nullptr; }
-        ds.gate_cap = 0;
-        HIP_TRY(hipMalloc(&ds.d_gate, need));
-        ds.gate_cap = need;
-    }
-    HIP_TRY(hipMemcpyAsync(ds.d_gate, cols, ptr_b, hipMemcpyHostToDevice,
+    RC_TRY(ds.d_gate.reserve(need));
+    uint8_t* const d_gate = ds.d_gate.ptr;
+    HIP_TRY(hipMemcpyAsync(d_gate, cols, ptr_b, hipMemcpyHostToDevice,
                            ds.stream));
     if (con_b)
-        HIP_TRY(hipMemcpyAsync(ds.d_gate + ptr_b, consts, con_b,
+        HIP_TRY(hipMemcpyAsync(d_gate + ptr_b, consts, con_b,
                                hipMemcpyHostToDevice, ds.stream));
-    HIP_TRY(hipMemcpyAsync(ds.d_gate + ptr_b + con_b, program, prg_b,
+    HIP_TRY(hipMemcpyAsync(d_gate + ptr_b + con_b, program, prg_b,
                            hipMemcpyHostToDevice, ds.stream));
     fp256 yv;
     ff_set_zero(yv);
@@ -458,9 +454,9 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
     hipLaunchKernelGGL(k_fr_gate_eval,
                        dim3((uint32_t)((n + GATE_THREADS - 1) / GATE_THREADS)),
                        dim3(GATE_THREADS), lds_bytes, ds.stream,
-                       (const fp256* const*)ds.d_gate,
-                       (const fp256*)(ds.d_gate + ptr_b),
-                       (const uint32_t*)(ds.d_gate + ptr_b + con_b), nops, n,
+                       (const fp256* const*)d_gate,
+                       (const fp256*)(d_gate + ptr_b),
+                       (const uint32_t*)(d_gate + ptr_b + con_b), nops, n,
                        rot_scale, y ? 1 : 0, yv, d_out);
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
@@ -517,26 +513,17 @@ static int build_tables(DeviceState& ds, const fp256& base, fp256* out,
     return 0;
 }
 
-// build-or-get the cached twiddle plan for (omega, log_n)
-static int get_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
-                    NttPlan** out) {
-    std::array<uint8_t, 40> key{};
-    memcpy(key.data(), omega.l, 32);
-    memcpy(key.data() + 32, &log_n, 4);
-    auto it = ds.plans.find(key);
-    if (it != ds.plans.end()) {
-        *out = &it->second;
-        return 0;
-    }
-    NttPlan p;
+// choose the split and build the twiddle tables for (omega, log_n) into p
+static int build_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
+                      NttPlan& p) {
     const bool force3 = getenv("SPECTRE_NTT_FORCE3") != nullptr;
     const uint32_t t1n = (log_n < TW_LOW_BITS) ? (1u << log_n) : (1u << TW_LOW_BITS);
     const uint32_t t2n = (log_n > TW_LOW_BITS) ? (1u << (log_n - TW_LOW_BITS)) : 1;
-    HIP_TRY(hipMalloc(&p.twB, ((uint64_t)t1n + t2n) * sizeof(fp256)));  // T1||T2
+    RC_TRY(p.twB.reserve((size_t)t1n + t2n));  // T1||T2
     fp256 wT2;
     host_pow_u32(wT2, omega, 1u << TW_LOW_BITS);
-    build_tables(ds, omega, p.twB, t1n);
-    build_tables(ds, wT2, p.twB + t1n, t2n);
+    build_tables(ds, omega, p.twB.ptr, t1n);
+    build_tables(ds, wT2, p.twB.ptr + t1n, t2n);
     if (log_n > 24 || (force3 && log_n >= 3)) {
         // three-pass split n = A*B*C, each axis <= 2^12 (balanced), or
         // SPECTRE_NTT_SPLIT3=max: kA = 12 so pass A gets 4096-elem tiles
@@ -560,12 +547,12 @@ static int get_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
         host_pow_u32(w1, omega, 1u << (p.k2 + p.k3));  // w^(B*C)
         host_pow_u32(w2, omega, 1u << (p.k1 + p.k3));  // w^(A*C)
         host_pow_u32(w3, omega, 1u << (p.k1 + p.k2));  // w^(A*B)
-        HIP_TRY(hipMalloc(&p.tw1, (1u << (p.k1 - 1)) * sizeof(fp256)));
-        HIP_TRY(hipMalloc(&p.tw2, (1u << (p.k2 - 1)) * sizeof(fp256)));
-        HIP_TRY(hipMalloc(&p.tw3, (1u << (p.k3 - 1)) * sizeof(fp256)));
-        build_tables(ds, w1, p.tw1, 1u << (p.k1 - 1));
-        build_tables(ds, w2, p.tw2, 1u << (p.k2 - 1));
-        build_tables(ds, w3, p.tw3, 1u << (p.k3 - 1));
+        RC_TRY(p.tw1.reserve(1u << (p.k1 - 1)));
+        RC_TRY(p.tw2.reserve(1u << (p.k2 - 1)));
+        RC_TRY(p.tw3.reserve(1u << (p.k3 - 1)));
+        build_tables(ds, w1, p.tw1.ptr, 1u << (p.k1 - 1));
+        build_tables(ds, w2, p.tw2.ptr, 1u << (p.k2 - 1));
+        build_tables(ds, w3, p.tw3.ptr, 1u << (p.k3 - 1));
     } else {
         // 2-pass split, k2 >= k1 (the contiguous row pass gets the bigger
         // tile). Measured on MI355X: k2 = 12 (4096-elem row tiles -> radix-4
@@ -586,16 +573,34 @@ static int get_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
         host_pow_u32(w1, omega, n2);  // root of column DFT
         host_pow_u32(w2, omega, n1);  // root of row DFT
         if (p.k1) {
-            HIP_TRY(hipMalloc(&p.tw1, (n1 / 2) * sizeof(fp256)));
-            build_tables(ds, w1, p.tw1, n1 / 2);
+            RC_TRY(p.tw1.reserve(n1 / 2));
+            build_tables(ds, w1, p.tw1.ptr, n1 / 2);
         }
-        HIP_TRY(hipMalloc(&p.tw2, (n2 / 2 ? n2 / 2 : 1) * sizeof(fp256)));
-        build_tables(ds, w2, p.tw2, n2 / 2 ? n2 / 2 : 1);
+        RC_TRY(p.tw2.reserve(n2 / 2 ? n2 / 2 : 1));
+        build_tables(ds, w2, p.tw2.ptr, n2 / 2 ? n2 / 2 : 1);
     }
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
-    auto res = ds.plans.emplace(key, p);
-    *out = &res.first->second;
+    return 0;
+}
+
+// build-or-get the cached twiddle plan for (omega, log_n)
+static int get_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
+                    NttPlan** out) {
+    std::array<uint8_t, 40> key{};
+    memcpy(key.data(), omega.l, 32);
+    memcpy(key.data() + 32, &log_n, 4);
+    auto it = ds.plans.find(key);
+    if (it == ds.plans.end()) {
+        NttPlan p;  // cached only once complete; a failed build frees it
+        const int rc = build_plan(ds, omega, log_n, p);
+        if (rc) {
+            p.release();
+            return rc;
+        }
+        it = ds.plans.emplace(key, p).first;
+    }
+    *out = &it->second;
     return 0;
 }
 
@@ -610,28 +615,19 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
     if (log_n == 0) return 0;  // DFT of size 1 is the identity; n^{-1} = 1, g^0 = 1
     const uint64_t n = 1ull << log_n;
     NttPlan* plan = nullptr;
-    int rc = get_plan(ds, omega, log_n, &plan);
-    if (rc) return rc;
+    RC_TRY(get_plan(ds, omega, log_n, &plan));
     const uint32_t n1 = 1u << plan->k1, n2 = 1u << plan->k2;
     const uint32_t t1n = (log_n < TW_LOW_BITS) ? (uint32_t)n : (1u << TW_LOW_BITS);
     const uint32_t t2n = (log_n > TW_LOW_BITS) ? (uint32_t)(n >> TW_LOW_BITS) : 1;
-    // scratch
-    if (ds.ntt_cap < n) {
-        if (ds.d_ntt_tmp) (void)hipFree(ds.d_ntt_tmp);
-        HIP_TRY(hipMalloc(&ds.d_ntt_tmp, n * sizeof(fp256)));
-        ds.ntt_cap = n;
-    }
+    RC_TRY(ds.d_ntt_tmp.reserve(n));
+    fp256* const tmp = ds.d_ntt_tmp.ptr;
     // coset power tables (per call; tiny)
     fp256* cT1 = nullptr;
     fp256* cT2 = nullptr;
     if (coset_gen) {
-        if (ds.coset_cap < (size_t)t1n + t2n) {
-            if (ds.d_cosetA) (void)hipFree(ds.d_cosetA);
-            HIP_TRY(hipMalloc(&ds.d_cosetA, ((size_t)t1n + t2n) * sizeof(fp256)));
-            ds.coset_cap = (size_t)t1n + t2n;
-        }
-        cT1 = ds.d_cosetA;
-        cT2 = ds.d_cosetA + t1n;
+        RC_TRY(ds.d_cosetA.reserve((size_t)t1n + t2n));
+        cT1 = ds.d_cosetA.ptr;
+        cT2 = cT1 + t1n;
         fp256 gT2;
         host_pow_u32(gT2, *coset_gen, 1u << TW_LOW_BITS);
         build_tables(ds, *coset_gen, cT1, t1n);
@@ -673,8 +669,8 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
         const uint32_t A = 1u << kA, B = 1u << kB, C = 1u << kC;
         fp256 one;
         ff_set_one<Fr>(one);
-        const fp256* T1 = plan->twB;
-        const fp256* T2 = plan->twB + t1n;
+        const fp256* T1 = plan->twB.ptr;
+        const fp256* T2 = plan->twB.ptr + t1n;
         auto tdim = tdiv;
         // radix-4 instantiation only when every thread gets a quad
         auto axis = [](uint32_t L, uint32_t threads) {
@@ -682,15 +678,15 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
                                                        : k_ntt_axis<false>;
         };
         hipLaunchKernelGGL(axis(A, tdim(A)), dim3(B * C), dim3(tdim(A)),
-                           LDS_BYTES(A), st, d_data, ds.d_ntt_tmp, plan->tw1,
+                           LDS_BYTES(A), st, d_data, tmp, plan->tw1.ptr,
                            T1, T2, fwd_cT1, fwd_cT2, /*coset_on_load=*/1, one,
                            0, kA, kB + kC, /*post_mode=*/1, 0, 0, 0, 0, 0);
         hipLaunchKernelGGL(axis(B, tdim(B)), dim3(A * C), dim3(tdim(B)),
-                           LDS_BYTES(B), st, ds.d_ntt_tmp, ds.d_ntt_tmp,
-                           plan->tw2, T1, T2, nullptr, nullptr, 0, one, 0, kB,
-                           kC, /*post_mode=*/2, kA, kC, 0, 0, 0);
+                           LDS_BYTES(B), st, tmp, tmp, plan->tw2.ptr, T1, T2,
+                           nullptr, nullptr, 0, one, 0, kB, kC,
+                           /*post_mode=*/2, kA, kC, 0, 0, 0);
         hipLaunchKernelGGL(axis(C, tdim(C)), dim3(A * B), dim3(tdim(C)),
-                           LDS_BYTES(C), st, ds.d_ntt_tmp, d_data, plan->tw3,
+                           LDS_BYTES(C), st, tmp, d_data, plan->tw3.ptr,
                            T1, T2, inv_cT1, inv_cT2, /*coset_on_load=*/0,
                            scale, inverse ? 1 : 0, kC, 0, /*post_mode=*/0, 0,
                            0, /*final_scatter=*/1, A, B);
@@ -701,14 +697,14 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
                                                            : k_ntt_col<false>,
                            dim3(n2), dim3(tc),
                            LDS_BYTES(n1), st, d_data,
-                           ds.d_ntt_tmp, plan->tw1, plan->twB,
-                           plan->twB + t1n, fwd_cT1, fwd_cT2, plan->k1,
+                           tmp, plan->tw1.ptr, plan->twB.ptr,
+                           plan->twB.ptr + t1n, fwd_cT1, fwd_cT2, plan->k1,
                            plan->k2);
         hipLaunchKernelGGL((!kForceRadix2 && n2 >= 4 * tr) ? k_ntt_row<true>
                                                            : k_ntt_row<false>,
                            dim3(n1), dim3(tr),
-                           LDS_BYTES(n2), st, ds.d_ntt_tmp,
-                           d_data, plan->tw2, inv_cT1, inv_cT2,
+                           LDS_BYTES(n2), st, tmp,
+                           d_data, plan->tw2.ptr, inv_cT1, inv_cT2,
                            /*coset_on_load=*/0, scale, inverse ? 1 : 0,
                            plan->k1, plan->k2);
     } else {
@@ -720,7 +716,7 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
                                                             : k_ntt_row<false>,
                            dim3(1), dim3(t1p),
                            LDS_BYTES(n2), st, d_data, d_data,
-                           plan->tw2, cc1, cc2,
+                           plan->tw2.ptr, cc1, cc2,
                            /*coset_on_load=*/inverse ? 0 : 1, scale,
                            inverse ? 1 : 0, 0, plan->k2);
     }

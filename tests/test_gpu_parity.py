@@ -246,6 +246,143 @@ def test_msm_device_resident(gpu, oracle):
     assert got == oracle.msm(bs, sc, n)
 
 
+# ---------------------------------------------- scratch growth, slot hand-off
+@pytest.fixture
+def fresh_gpu():
+    """A context of its own, so the scratch starts empty and no slot is busy."""
+    from spectre_amd import SpectreGpu
+    g = SpectreGpu([0])
+    yield g
+    g.close()
+
+
+def _device_inputs(g, bs, sc):
+    d_b = g.malloc(len(bs))
+    d_s = g.malloc(len(sc))
+    g.upload(d_b, bs)
+    g.upload(d_s, sc)
+    return d_b, d_s
+
+
+def test_msm_scratch_regrowth_sequence(fresh_gpu, oracle):
+    """Walks every MSM scratch group of one context through grow, reuse and
+    grow again (entries, side arrays, buckets, sort temp, pinned sums, the
+    host-pointer scalars/bases and the bases cache); every result bit-exact
+    against the oracle."""
+    from spectre_amd import ffi
+    g = fresh_gpu
+
+    def inputs(n, seed):
+        sc, bs = oracle.gen_msm_inputs(n, seed, fast=True)
+        return sc, bs, oracle.msm(bs, sc, n)
+
+    small = inputs(64, 9101)
+    big = inputs(4096, 9102)
+    for n, (sc, bs, want) in ((64, small), (4096, big), (64, small)):
+        assert g.msm(bs, sc, n) == want, n
+    # batch: more windows' worth of buckets than any single call
+    n = 257
+    _, bs = oracle.gen_msm_inputs(n, 9103, fast=True)
+    vecs = [oracle.gen_msm_inputs(n, 9104 + b, fast=True)[0] for b in range(3)]
+    assert g.msm_batch(bs, b"".join(vecs), 3, n) == [
+        oracle.msm(bs, sc, n) for sc in vecs]
+    # 4 entries per thread: more accumulate threads, so larger side arrays,
+    # than the auto choice (>= MSM_ACC_E_MIN) gave the same n above
+    g.set_msm_acc_entries(4)
+    sc, bs, want = big
+    assert g.msm(bs, sc, 4096) == want
+    g.set_msm_acc_entries(0)
+    # window shards on the shrunk-again scratch, spliced into the full-range
+    # shard's other windows (window sums are Jacobian: compare the affine)
+    n = 1000
+    sc, bs, want = inputs(n, 9110)
+    d_b, d_s = _device_inputs(g, bs, sc)
+    blob = bytearray(g.msm_shard_device(d_b, d_s, n))
+    for w_lo in (4, 12):
+        blob[96 * w_lo:96 * (w_lo + 4)] = g.msm_shard_windows_device(
+            d_b, d_s, n, w_lo, 4)
+    assert ffi.combine_window_partials(bytes(blob), 1) == want
+    g.free(d_b)
+    g.free(d_s)
+    # cached bases: upload on the miss, no bases needed on the hit
+    n = 300
+    sc, bs, want = inputs(n, 9111)
+    assert g.msm(bs, sc, n, bases_id=91) == want
+    assert g.msm(None, sc, n, bases_id=91) == want
+
+
+def test_ntt_scratch_regrowth_sequence(fresh_gpu, oracle, golden):
+    """NTT io/tmp/coset scratch and the plan cache of one context: small,
+    large, small again with a coset, large inverse with a coset."""
+    g = fresh_gpu
+    g5 = oracle.fr_from_canonical((5).to_bytes(32, "little"))
+    for log_n, inverse, coset in ((4, False, None), (13, False, None),
+                                  (4, False, g5), (13, True, g5)):
+        a = oracle.gen_fr_vector(1 << log_n, 9200 + log_n)
+        w = _omega(log_n, oracle, golden)
+        if inverse:
+            w = oracle.fr_inv(w)
+        got = g.ntt(a, log_n, w, inverse=inverse, coset_gen=coset)
+        assert got == oracle.ntt(a, log_n, w, inverse=inverse,
+                                 coset_gen=coset), (log_n, inverse)
+
+
+def _pipe_slots():
+    import os
+    return min(max(int(os.environ.get("SPECTRE_PIPE_SLOTS", "3")), 1), 3)
+
+
+def test_msm_async_slot_exhaustion_is_loud(fresh_gpu, oracle):
+    """Enqueueing without waiting wraps round to the busy slot 0 at attempt
+    slots + 1: that call is rejected by return code (no kernel runs), every
+    accepted call still delivers, and the context stays usable."""
+    from spectre_amd import ffi
+    g = fresh_gpu
+    n = 257
+    sc, bs = oracle.gen_msm_inputs(n, 9301, fast=True)
+    want = oracle.msm(bs, sc, n)
+    d_b, d_s = _device_inputs(g, bs, sc)
+    sync_partials = g.msm_shard_device(d_b, d_s, n)
+    assert ffi.combine_partials(sync_partials, 1) == want
+    pend, rejected = [], []
+    for attempt in range(1, 5):
+        try:
+            pend.append(g.msm_shard_device_async(d_b, d_s, n))
+        except RuntimeError as e:
+            assert "already has a call in flight" in str(e)
+            rejected.append(attempt)
+            break
+    assert rejected == [_pipe_slots() + 1]
+    assert [slot for _, slot in pend] == list(range(_pipe_slots()))
+    for buf, slot in pend:
+        g.msm_slot_wait(slot)
+        assert ffi.combine_partials(bytes(buf), 1) == want, slot
+    assert g.msm_shard_device(d_b, d_s, n) == sync_partials
+    g.free(d_b)
+    g.free(d_s)
+
+
+def test_msm_sync_on_busy_slot_is_rejected(fresh_gpu, oracle):
+    """A synchronous call shares slot 0 with the first async call: while that
+    one is pending it must be rejected, not overwrite the pending window
+    sums; after the wait both deliver."""
+    from spectre_amd import ffi
+    g = fresh_gpu
+    n = 257
+    sc, bs = oracle.gen_msm_inputs(n, 9302, fast=True)
+    want = oracle.msm(bs, sc, n)
+    d_b, d_s = _device_inputs(g, bs, sc)
+    buf, slot = g.msm_shard_device_async(d_b, d_s, n)
+    assert slot == 0
+    with pytest.raises(RuntimeError, match="already has a call in flight"):
+        g.msm_shard_device(d_b, d_s, n)
+    g.msm_slot_wait(0)
+    assert ffi.combine_partials(bytes(buf), 1) == want
+    assert ffi.combine_partials(g.msm_shard_device(d_b, d_s, n), 1) == want
+    g.free(d_b)
+    g.free(d_s)
+
+
 # ---------------------------------------------------------------- NTT
 def test_ntt_inline_golden(gpu, golden):
     for c in golden("ntt.json")["inline_cases"]:
