@@ -24,7 +24,8 @@
  * library REQUIRES a visible AMD GPU for every compute entry point (there is
  * deliberately no CPU fallback — a missing GPU fails loudly); the only
  * host-only entry points are spectre_gpu_msm_g1_combine(_windows),
- * spectre_gpu_msm_acc_auto_entries and the format/version queries.
+ * spectre_gpu_msm_acc_auto_entries, spectre_gpu_fr_scan_tile_default and the
+ * format/version queries.
  */
 #ifndef SPECTRE_GPU_H
 #define SPECTRE_GPU_H
@@ -226,6 +227,30 @@ int spectre_gpu_fr_vec_op(spectre_gpu_ctx*, int dev, int op,
                           const void* d_a, const void* d_b /* NULL for op 3 */,
                           const uint8_t c[32] /* NULL for ops 0-2 */,
                           void* d_out, uint64_t n);
+
+/* ---- grand products (device buffers, Montgomery Fr) ---------------------
+ * The permutation and lookup arguments build, per column,
+ *   Z[0] = 1 (or the previous chunk's last value), Z[i+1] = Z[i]*num[i]/den[i]
+ * which halo2 computes with batch_invert, a pointwise multiply and a serial
+ * running product. These two calls keep that stage on the device. All
+ * buffers are device pointers on device `dev`; the calls synchronize. */
+/* out[i] = in[i]^-1; a zero element stays zero (ff::BatchInvert / halo2
+ * batch_invert semantics). d_out may alias d_in. */
+int spectre_gpu_fr_batch_invert(spectre_gpu_ctx*, int dev, const void* d_in,
+                                void* d_out, uint64_t n);
+/* z[0] = z0, z[i] = z0 * prod_{j<i} num[j] * den[j]^-1   for i < n;
+ * out_last = z0 * prod_{j<n} ...  (the value halo2 carries into the next
+ * permutation chunk). d_den == NULL: no denominators. z0 == NULL: one.
+ * out_last may be NULL. A zero denominator inverts to zero (as above), so
+ * every later z is zero. d_z may alias d_num or d_den. n <= 2^28. */
+int spectre_gpu_fr_grand_product(spectre_gpu_ctx*, int dev, const void* d_num,
+                                 const void* d_den, const uint8_t z0[32],
+                                 void* d_z, uint64_t n, uint8_t out_last[32]);
+/* Elements per workgroup tile of the two kernels above. 0 (default) = the
+ * built-in choice; otherwise a multiple of the block size (256) up to the
+ * default (tests, tuning). Result bytes do not depend on it. */
+int spectre_gpu_set_fr_scan_tile(spectre_gpu_ctx*, uint32_t elems);
+uint32_t spectre_gpu_fr_scan_tile_default(void); /* host-only, pure */
 
 /* ---- device memory helpers (for C callers and the bench harness) ------- */
 int spectre_gpu_malloc(spectre_gpu_ctx*, int dev, size_t bytes, void** d_ptr);

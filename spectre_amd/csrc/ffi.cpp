@@ -540,6 +540,54 @@ int spectre_gpu_fr_vec_op(spectre_gpu_ctx* ctx, int dev, int op,
                             (fp256*)d_out, n);
 }
 
+// ---------------------------------------------------------------- grand products
+int spectre_gpu_fr_batch_invert(spectre_gpu_ctx* ctx, int dev,
+                                const void* d_in, void* d_out, uint64_t n) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_in || !d_out) {
+        set_err("fr_batch_invert: null device pointer");
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    return fr_batch_invert_device(ctx, dev, (const fp256*)d_in, (fp256*)d_out,
+                                  n);
+}
+
+int spectre_gpu_fr_grand_product(spectre_gpu_ctx* ctx, int dev,
+                                 const void* d_num, const void* d_den,
+                                 const uint8_t z0[32], void* d_z, uint64_t n,
+                                 uint8_t out_last[32]) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_num || !d_z) {
+        set_err("fr_grand_product: null device pointer");
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 seed, last;
+    if (z0) ff_from_bytes(seed, z0);
+    else ff_set_one<Fr>(seed);
+    RC_TRY(fr_grand_product_device(ctx, dev, (const fp256*)d_num,
+                                   (const fp256*)d_den, seed, (fp256*)d_z, n,
+                                   out_last ? &last : nullptr));
+    if (out_last) ff_to_bytes(out_last, last);
+    return 0;
+}
+
+int spectre_gpu_set_fr_scan_tile(spectre_gpu_ctx* ctx, uint32_t elems) {
+    if (!ctx || !fr_scan_tile_valid(elems)) {
+        set_err("set_fr_scan_tile: %u is not 0 or a multiple of 256 <= %u",
+                elems, fr_scan_tile_default());
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    ctx->fr_scan_tile = elems;
+    return 0;
+}
+
+uint32_t spectre_gpu_fr_scan_tile_default(void) {
+    return fr_scan_tile_default();
+}
+
 // ---------------------------------------------------------------- memory
 int spectre_gpu_malloc(spectre_gpu_ctx* ctx, int dev, size_t bytes,
                        void** d_ptr) {

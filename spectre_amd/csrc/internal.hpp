@@ -155,12 +155,16 @@ struct DeviceState {
     DevBuf<fp256> d_cosetA;   // coset power tables T1 || T2
     // ---- gate-eval scratch (column pointers, constants, program; bytes) ----
     DevBuf<uint8_t> d_gate;
+    // ---- grand-product scratch: tile products -> prefixes (+ the grand
+    // total in the last slot), and the pinned landing spot of that total ----
+    DevBuf<fp256> d_gp_prods;
+    PinnedBuf<fp256> h_gp_last;
     std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n||inverse
     // frees everything this device owns; the caller has made it current
     void release() {
         for (auto& sl : slots) sl.release(stream);
         release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
-                    d_ntt_io, d_cosetA, d_gate);
+                    d_ntt_io, d_cosetA, d_gate, d_gp_prods, h_gp_last);
         for (auto& kv : bases_cache) kv.second.release();
         bases_cache.clear();
         for (auto& kv : plans) kv.second.release();
@@ -178,6 +182,7 @@ struct spectre_gpu_ctx {
     std::vector<DeviceState> devs;
     std::recursive_mutex mu;
     uint32_t msm_acc_entries = 0;  // entries per accumulate thread, 0 = auto
+    uint32_t fr_scan_tile = 0;     // elements per poly.hip tile, 0 = default
 };
 
 // One MSM pipeline run: nbatch scalar vectors (batch-major, nbatch*n*32 B)
@@ -228,3 +233,18 @@ int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
 // ntt.hip — in-place NTT on a device buffer (synchronizes the stream).
 int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
                const fp256& omega, int inverse, const fp256* coset_gen);
+
+// poly.hip — out[i] = in[i]^-1, zero staying zero (synchronizes). d_out may
+// alias d_in.
+int fr_batch_invert_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
+                           fp256* d_out, uint64_t n);
+// poly.hip — z[i] = z0 * prod_{j<i} num[j] * den[j]^-1 (d_den may be null),
+// *out_last (may be null) = the i = n value (synchronizes). d_z may alias
+// d_num or d_den.
+int fr_grand_product_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_num,
+                            const fp256* d_den, const fp256& z0, fp256* d_z,
+                            uint64_t n, fp256* out_last);
+// poly.hip — the built-in tile of the two calls above, and whether a
+// ctx->fr_scan_tile value is usable (pure; host).
+uint32_t fr_scan_tile_default();
+bool fr_scan_tile_valid(uint32_t elems);

@@ -128,6 +128,19 @@ def load_library() -> ctypes.CDLL:
         c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
         c.c_void_p, c.c_uint64,
     ]
+    lib.spectre_gpu_fr_batch_invert.restype = c.c_int
+    lib.spectre_gpu_fr_batch_invert.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_uint64,
+    ]
+    lib.spectre_gpu_fr_grand_product.restype = c.c_int
+    lib.spectre_gpu_fr_grand_product.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_uint64, c.c_void_p,
+    ]
+    lib.spectre_gpu_set_fr_scan_tile.restype = c.c_int
+    lib.spectre_gpu_set_fr_scan_tile.argtypes = [c.c_void_p, c.c_uint32]
+    lib.spectre_gpu_fr_scan_tile_default.restype = c.c_uint32
+    lib.spectre_gpu_fr_scan_tile_default.argtypes = []
     lib.spectre_gpu_malloc.restype = c.c_int
     lib.spectre_gpu_malloc.argtypes = [c.c_void_p, c.c_int, c.c_size_t,
                                        c.POINTER(c.c_void_p)]
@@ -154,6 +167,12 @@ def msm_acc_auto_entries(entries: int, cus: int, resident_blocks: int) -> int:
     accumulate thread (see spectre_gpu_set_msm_acc_entries)."""
     return load_library().spectre_gpu_msm_acc_auto_entries(
         entries, cus, resident_blocks)
+
+
+def fr_scan_tile_default() -> int:
+    """Host-only: the built-in elements per workgroup tile of
+    fr_batch_invert / fr_grand_product (see set_fr_scan_tile)."""
+    return load_library().spectre_gpu_fr_scan_tile_default()
 
 
 def combine_window_partials(partials: bytes, nshards: int) -> bytes:
@@ -406,6 +425,36 @@ class SpectreGpu:
             ctypes.c_void_p(d_b) if d_b else None, cc,
             ctypes.c_void_p(d_out), n)
         self._check(rc, "fr_vec_op")
+
+    def fr_batch_invert(self, d_in: int, d_out: int, n: int,
+                        dev: int = 0) -> None:
+        """d_out[i] = d_in[i]^-1 over n Montgomery Fr elements; zero stays
+        zero. d_out may equal d_in."""
+        rc = self._lib.spectre_gpu_fr_batch_invert(
+            self._ctx, dev, ctypes.c_void_p(d_in), ctypes.c_void_p(d_out), n)
+        self._check(rc, "fr_batch_invert")
+
+    def fr_grand_product(self, d_num: int, d_den: int | None,
+                         z0: bytes | None, d_z: int, n: int,
+                         dev: int = 0) -> bytes:
+        """d_z[i] = z0 * prod_{j<i} num[j] / den[j] for i < n (d_den None: no
+        denominators; z0 None: one). Returns the i = n value, which seeds the
+        next chunk. d_z may equal d_num or d_den."""
+        seed = (ctypes.c_uint8 * 32).from_buffer_copy(z0) if z0 else None
+        last = (ctypes.c_uint8 * 32)()
+        rc = self._lib.spectre_gpu_fr_grand_product(
+            self._ctx, dev, ctypes.c_void_p(d_num),
+            ctypes.c_void_p(d_den) if d_den else None, seed,
+            ctypes.c_void_p(d_z), n, last)
+        self._check(rc, "fr_grand_product")
+        return bytes(last)
+
+    def set_fr_scan_tile(self, elems: int) -> None:
+        """Fix the elements per workgroup tile of the two calls above (a
+        multiple of 256 up to fr_scan_tile_default()); 0 restores the
+        default. Results do not change."""
+        rc = self._lib.spectre_gpu_set_fr_scan_tile(self._ctx, elems)
+        self._check(rc, "set_fr_scan_tile")
 
     # ---- device memory helpers ----
     def malloc(self, nbytes: int, dev: int = 0) -> int:
