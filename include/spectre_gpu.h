@@ -24,8 +24,8 @@
  * library REQUIRES a visible AMD GPU for every compute entry point (there is
  * deliberately no CPU fallback — a missing GPU fails loudly); the only
  * host-only entry points are spectre_gpu_msm_g1_combine(_windows),
- * spectre_gpu_msm_acc_auto_entries, spectre_gpu_fr_scan_tile_default and the
- * format/version queries.
+ * spectre_gpu_msm_acc_auto_entries, spectre_gpu_msm_fold_window,
+ * spectre_gpu_fr_scan_tile_default and the format/version queries.
  */
 #ifndef SPECTRE_GPU_H
 #define SPECTRE_GPU_H
@@ -132,6 +132,15 @@ int spectre_gpu_set_msm_acc_entries(spectre_gpu_ctx*, uint32_t e);
  * `resident_blocks` accumulate workgroups resident on each. */
 uint32_t spectre_gpu_msm_acc_auto_entries(uint64_t entries, uint32_t cus,
                                           uint32_t resident_blocks);
+/* The device reduction tail leaves three Jacobian partials per window, and
+ * the library folds them on the host before it hands out window sums:
+ *   out = p0 + SPECTRE_MSM_TAIL_CHUNK * (p1 + SPECTRE_MSM_TAIL_LO * p2).
+ * This is that fold (host-only, pure; 96 B Jacobian each, out may alias an
+ * input). Callers of the MSM entry points never see the partials. */
+#define SPECTRE_MSM_TAIL_CHUNK 8u /* buckets per chunk of the default build */
+#define SPECTRE_MSM_TAIL_LO 64u   /* columns of a window's chunk grid */
+int spectre_gpu_msm_fold_window(const uint8_t p0[96], const uint8_t p1[96],
+                                const uint8_t p2[96], uint8_t out[96]);
 /* Combine gathered shard partials (host-only, deterministic rank order):
  * partials = nshards * NUM_WINDOWS * 96 B. */
 int spectre_gpu_msm_g1_combine(const uint8_t* partials, uint32_t nshards,

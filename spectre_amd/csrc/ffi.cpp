@@ -93,6 +93,21 @@ uint32_t spectre_gpu_msm_acc_auto_entries(uint64_t entries, uint32_t cus,
     return msm_acc_auto_entries(entries, cus, resident_blocks);
 }
 
+int spectre_gpu_msm_fold_window(const uint8_t p0[96], const uint8_t p1[96],
+                                const uint8_t p2[96], uint8_t out[96]) {
+    if (!p0 || !p1 || !p2 || !out) {
+        set_err("msm_fold_window: null argument");
+        return -1;
+    }
+    g1_jac p[3], sum;
+    memcpy(&p[0], p0, 96);
+    memcpy(&p[1], p1, 96);
+    memcpy(&p[2], p2, 96);
+    msm_fold_window(p[0], p[1], p[2], sum);
+    memcpy(out, &sum, 96);
+    return 0;
+}
+
 // ---------------------------------------------------------------- staging
 #define STAGE_CHUNK (16u << 20)
 

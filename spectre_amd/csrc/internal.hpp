@@ -22,8 +22,17 @@
 #define MSM_NWIN 16                        // ceil(255 / WBITS)
 #define MSM_BPW (1u << (MSM_WBITS - 1))    // buckets per window
 #ifndef MSM_CHUNK
-#define MSM_CHUNK 8                        // buckets per reduction thread
+#define MSM_CHUNK SPECTRE_MSM_TAIL_CHUNK   // buckets per reduction thread
 #endif
+// The reduction tail splits a window's chunk index c = MSM_LO * hi + lo and
+// weights the row and column sums of the chunk totals instead of lifting
+// every chunk on its own (msm.hip, kernels 5 and 6).
+#define MSM_CPW (MSM_BPW / MSM_CHUNK)      // chunks per window
+#define MSM_LO SPECTRE_MSM_TAIL_LO         // columns of the chunk grid
+#define MSM_HI (MSM_CPW / MSM_LO)          // rows of the chunk grid
+static_assert(MSM_CPW % MSM_LO == 0, "chunks per window: a multiple of MSM_LO");
+static_assert((MSM_CHUNK & (MSM_CHUNK - 1)) == 0 && (MSM_LO & (MSM_LO - 1)) == 0,
+              "the host fold multiplies by doubling");
 // Sorted entries per accumulate thread are a per-call value (a multiple of
 // 4): ctx->msm_acc_entries when set, else msm_acc_auto_entries() within
 // these bounds.
@@ -111,12 +120,13 @@ struct MsmSlot {
     // grow together:
     DevBuf<uint32_t> d_offsets;  // nbt + 1 segment bounds
     DevBuf<g1_jac> d_buckets;    // nbt
-    DevBuf<g1_jac> d_red;        // nbt/MSM_CHUNK chunk sums, then the
-                                 // nbatch * w_cnt window sums
-    // Window sums come back through a PINNED per-slot buffer: an async D2H
-    // into caller (pageable) memory silently blocks the calling thread on
-    // ROCm, which serialized the whole slot pipeline in r2's first
-    // measurement. msm_slot_drain memcpys pinned -> caller.
+    DevBuf<g1_jac> d_red;        // nbt/MSM_CHUNK weighted chunk sums W,
+                                 // as many plain chunk sums T, then three
+                                 // partials for each of nbatch * w_cnt windows
+    // The window partials (3 per window) come back through a PINNED per-slot
+    // buffer: an async D2H into caller (pageable) memory silently blocks the
+    // calling thread on ROCm, which serialized the whole slot pipeline in
+    // r2's first measurement. msm_slot_drain folds pinned -> caller.
     PinnedBuf<g1_jac> h_wins;
     // Result hand-off, set by the enqueue and cleared by msm_slot_drain
     // (msm.hip) and nowhere else; non-null = the slot is busy.
@@ -215,8 +225,15 @@ int msm_device(spectre_gpu_ctx* ctx, int dev, const MsmCall& call,
 uint32_t msm_acc_auto_entries(uint64_t entries, uint32_t cus,
                               uint32_t resident_blocks);
 
-// msm.hip — sync a slot's stream and deliver pending window sums.
+// msm.hip — sync a slot's stream, fold the pending window partials and
+// deliver the window sums.
 int msm_slot_drain(spectre_gpu_ctx* ctx, int dev, int slot);
+
+// msm.hip — one window sum from the three partials the device tail yields:
+// out = p0 + MSM_CHUNK * (p1 + MSM_LO * p2) (pure; host). out may alias an
+// input.
+void msm_fold_window(const g1_jac& p0, const g1_jac& p1, const g1_jac& p2,
+                     g1_jac& out);
 
 // ntt.hip — gate-expression evaluator over device column buffers
 // (synchronizes). cols = host array of ncols device pointers.

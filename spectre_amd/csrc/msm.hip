@@ -26,12 +26,18 @@
 //                         k_bucket_fix. Deterministic by construction, and
 //                         the affine result is canonical, so ANY schedule
 //                         yields bit-identical output bytes.
-//   5. k_window_chunks  — per MSM_CHUNK consecutive buckets: weighted suffix
-//                         sum + double-and-add lift to the window offset.
-//   6. k_window_sum     — one block per (batch, window), pairwise LDS tree
-//                         to the final window sums in a single launch.
-// Host side (ffi.cpp) finishes each batch with the window Horner (~255
-// doublings + adds) and one field inversion to affine.
+//   5. k_window_chunks  — per MSM_CHUNK consecutive buckets: plain sum T_c
+//                         and locally weighted sum W_c from one suffix-sum
+//                         loop. No per-chunk lift to the window offset.
+//   6. k_window_tail    — three blocks per (batch, window) in one launch:
+//                         sum of the W_c, and the row and column sums of the
+//                         T_c (chunk index c = MSM_LO*hi + lo) weighted by
+//                         their 6-bit index; serial adds, then a pairwise
+//                         LDS tree.
+// Host side: msm_slot_drain folds the three partials of each window,
+// P0 + CHUNK*(P1 + MSM_LO*P2) (9 doublings + 2 adds); ffi.cpp finishes each
+// batch with the window Horner (~255 doublings + adds) and one field
+// inversion to affine.
 //
 // All field math is 8x32-limb Montgomery CIOS (ff.hpp) — VALU integer work
 // (measured at the chip's v_mad_u64_u32 issue ceiling); MFMA does not apply
@@ -290,23 +296,22 @@ ACC_KERNEL void k_bucket_fix(const uint32_t* __restrict__ off,
     buckets[b] = acc;
 }
 
-// ---- kernel 5: weighted chunk reduction -----------------------------------
-// Window-local bucket j has multiplier (j+1). For the chunk covering
-// window-local buckets [m, m+CHUNK):
-//   sum_j (j+1) B[m+j]  (suffix running sums)  +  m * sum_j B[m+j]
-// (double-and-add; m < 2^(WBITS-1)). Uniform in the flattened
+// ---- kernel 5: per-chunk sums ----------------------------------------------
+// Window-local bucket j has multiplier (j+1). Chunk c of a window covers the
+// window-local buckets [c*CHUNK, c*CHUNK+CHUNK); one thread per chunk forms,
+// with one suffix-sum loop (two adds per bucket),
+//   T_c = sum_j B[c*CHUNK+j]    and    W_c = sum_j (j+1) B[c*CHUNK+j].
+// The chunk's offset in the window is NOT applied here: lifting T_c by
+// c*CHUNK per chunk was half of this kernel's adds; kernel 6 applies the
+// offsets to 2*64 marginal sums per window instead. Uniform in the flattened
 // (batch*NWIN + w) window index, so batching needs no changes here.
 PT_KERNEL void k_window_chunks(const g1_jac* __restrict__ buckets,
                                uint32_t total_chunks,
-                               g1_jac* __restrict__ out) {
-    const uint32_t nchunks_pw = MSM_BPW / MSM_CHUNK;
+                               g1_jac* __restrict__ outW,
+                               g1_jac* __restrict__ outT) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total_chunks) return;
-    uint32_t cw = t % nchunks_pw;
     const g1_jac* B = buckets + (uint64_t)t * MSM_CHUNK;
-    // Phase order keeps at most TWO Jacobian accumulators live (3 would push
-    // past 256 VGPRs and spill): accW is parked in `out` before the
-    // double-and-add, then re-loaded for the final add.
     g1_jac accT, accW;
     g1j_set_inf(accT);
     g1j_set_inf(accW);
@@ -314,44 +319,90 @@ PT_KERNEL void k_window_chunks(const g1_jac* __restrict__ buckets,
         g1j_add_ip(accT, B[j]);
         g1j_add_ip(accW, accT);
     }
-    out[t] = accW;  // park; accW dead
-    const uint32_t m = cw * MSM_CHUNK;
-    if (m && !g1j_is_inf(accT)) {
-        g1_jac acc;
-        g1j_set_inf(acc);
-        for (int bit = MSM_WBITS - 1; bit >= 0; bit--) {
-            g1j_dbl_ip(acc);
-            if ((m >> bit) & 1) g1j_add_ip(acc, accT);
-        }
-        g1_jac w = out[t];  // accT dead; (w, acc) live
-        g1j_add_ip(w, acc);
-        out[t] = w;
-    }
+    outW[t] = accW;
+    outT[t] = accT;
 }
 
-// ---- kernel 6: per-window LDS-tree sum ------------------------------------
-// One block per flattened (batch, window) sums its BPW/CHUNK chunk points:
-// threads grid-stride their share, then a pairwise LDS tree — serial depth
-// ~16 adds in ONE launch (a 3-level cascade of tiny grids was ~0.8 ms of
-// launch+latency overhead).
-#define WSUM_THREADS 256
-__global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_sum(
-    const g1_jac* __restrict__ in, g1_jac* __restrict__ out) {
+// ---- kernel 6: per-window weighted sums -----------------------------------
+// With c = MSM_LO*hi + lo the window sum is
+//   sum_c W_c + CHUNK * ( sum_lo lo*R_lo + MSM_LO * sum_hi hi*C_hi ),
+// R_lo = sum_hi T_(hi,lo) the column sums and C_hi = sum_lo T_(hi,lo) the row
+// sums of the window's MSM_HI x MSM_LO grid of chunk totals. One block per
+// (window, role) yields one of the three partials
+//   role 0: P0 = sum_c W_c     role 1: P1 = sum_lo lo*R_lo
+//   role 2: P2 = sum_hi hi*C_hi
+// and the host folds them (msm_fold_window). All roles run the same code:
+// every thread sums its share serially (thread t = q*M + idx takes a q-th
+// of marginal idx, M = MSM_LO or MSM_HI marginals; role 0 grid-strides), a
+// pairwise LDS tree halves the live threads per level, and at the level
+// where M threads are left — each holding marginal idx = t — roles 1 and 2
+// multiply by idx with a log2(M)-bit double-and-add. Serial depth at
+// CHUNK = 8 with 512 threads (8 per marginal): 8 adds + 3 levels + a 6-bit
+// multiply (about 6) + 6 levels, about 23 add-equivalents, in ONE launch of
+// 3 blocks per window (a 3-level cascade of tiny grids was ~0.8 ms of
+// launch+latency overhead). Empty marginals skip their multiply, and every
+// add returns early on the identity.
+// MEASURED on MI355X: 512 against 256 threads (16 adds + 2 levels first)
+// takes the stage from 0.74 to 0.61 ms at every n and one synchronous call
+// at n = 2^12 from 1.42 to 1.31 ms; the pipelined throughput at n = 2^20 is
+// the same within its noise. 512 threads is two waves on each SIMD of a CU,
+// the 256-VGPR budget the kernel needs (220).
+#ifndef WSUM_THREADS
+#define WSUM_THREADS 512
+#endif
+static_assert(MSM_CPW % WSUM_THREADS == 0, "role 0 shares");
+static_assert(WSUM_THREADS % MSM_LO == 0 && MSM_HI % (WSUM_THREADS / MSM_LO) == 0,
+              "column shares");
+static_assert(MSM_HI <= WSUM_THREADS && WSUM_THREADS % MSM_HI == 0 &&
+              MSM_LO % (WSUM_THREADS / MSM_HI) == 0, "row shares");
+__global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_tail(
+    const g1_jac* __restrict__ inW, const g1_jac* __restrict__ inT,
+    g1_jac* __restrict__ out) {
     __shared__ g1_jac lds[WSUM_THREADS / 2];
-    const uint32_t per_win = MSM_BPW / MSM_CHUNK;
-    const uint32_t w = blockIdx.x;
+    const uint32_t w = blockIdx.x / 3, role = blockIdx.x % 3;
     const uint32_t t = threadIdx.x;
+    // marginals of this role, and this thread's share: cnt elements from
+    // src, stride apart
+    const uint32_t M = role == 0 ? 0 : role == 1 ? MSM_LO : MSM_HI;
+    const g1_jac* src;
+    uint32_t stride, cnt;
+    if (role == 0) {
+        src = inW + (uint64_t)w * MSM_CPW + t;
+        stride = WSUM_THREADS;
+        cnt = MSM_CPW / WSUM_THREADS;
+    } else if (role == 1) {  // column lo = t % LO, rows [q*cnt, q*cnt+cnt)
+        cnt = MSM_HI / (WSUM_THREADS / MSM_LO);
+        src = inT + (uint64_t)w * MSM_CPW + (t / MSM_LO) * cnt * MSM_LO +
+              t % MSM_LO;
+        stride = MSM_LO;
+    } else {  // row hi = t % HI, columns [q*cnt, q*cnt+cnt)
+        cnt = MSM_LO / (WSUM_THREADS / MSM_HI);
+        src = inT + (uint64_t)w * MSM_CPW + (t % MSM_HI) * MSM_LO +
+              (t / MSM_HI) * cnt;
+        stride = 1;
+    }
     g1_jac acc;
     g1j_set_inf(acc);
-    for (uint32_t j = t; j < per_win; j += blockDim.x)
-        g1j_add_ip(acc, in[(uint64_t)w * per_win + j]);
+    for (uint32_t j = 0; j < cnt; j++) g1j_add_ip(acc, src[(uint64_t)j * stride]);
     for (uint32_t k = WSUM_THREADS / 2; k >= 1; k >>= 1) {
+        if (2 * k == M && t < M) {  // acc = marginal t: acc *= t
+            if (t == 0) g1j_set_inf(acc);
+            if (!g1j_is_inf(acc)) {
+                g1_jac r;
+                g1j_set_inf(r);
+                for (uint32_t bit = M >> 1; bit; bit >>= 1) {
+                    g1j_dbl_ip(r);
+                    if (t & bit) g1j_add_ip(r, acc);
+                }
+                acc = r;
+            }
+        }
         if (t >= k && t < 2 * k) lds[t - k] = acc;
         __syncthreads();
         if (t < k) g1j_add_ip(acc, lds[t]);
         __syncthreads();
     }
-    if (t == 0) out[w] = acc;
+    if (t == 0) out[blockIdx.x] = acc;
 }
 
 // ---- host orchestration ---------------------------------------------------
@@ -415,7 +466,7 @@ static int ensure_msm_scratch(MsmSlot& ds, uint64_t ent, uint32_t nwin,
     RC_TRY(ds.d_lastP.reserve(nt));
     RC_TRY(ds.d_offsets.reserve(nbt + 1));
     RC_TRY(ds.d_buckets.reserve(nbt));
-    RC_TRY(ds.d_red.reserve(nbt / MSM_CHUNK + nwin));
+    RC_TRY(ds.d_red.reserve(2 * nbt / MSM_CHUNK + 3 * (uint64_t)nwin));
     size_t sort_need = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(
         nullptr, sort_need, ds.d_keys_in.ptr, ds.d_keys_out.ptr,
@@ -510,8 +561,8 @@ static int msm_acquire_slot(DeviceState& dstate, const MsmCall& c, int slot,
 }
 
 // Size the slot's scratch, launch the six stages and the D2H of the window
-// sums into the slot's pinned buffer, and mark the slot busy: msm_slot_drain
-// delivers the sums to winsums_host.
+// partials into the slot's pinned buffer, and mark the slot busy:
+// msm_slot_drain folds them into the window sums in winsums_host.
 static int msm_enqueue(spectre_gpu_ctx* ctx, DeviceState& dstate, MsmSlot& ds,
                        const MsmCall& c, g1_jac* winsums_host,
                        StageTimer& timer) {
@@ -524,7 +575,7 @@ static int msm_enqueue(spectre_gpu_ctx* ctx, DeviceState& dstate, MsmSlot& ds,
             : msm_acc_auto_entries(ent, (uint32_t)dstate.num_cus,
                                    (uint32_t)dstate.acc_resident_blocks);
     RC_TRY(ensure_msm_scratch(ds, ent, nw, acc_e));
-    RC_TRY(ds.h_wins.reserve(nw));
+    RC_TRY(ds.h_wins.reserve(3 * (size_t)nw));
     const uint32_t nbt = nw * MSM_BPW;
     const int canonical = (c.flags & SPECTRE_SCALARS_CANONICAL) ? 1 : 0;
     hipStream_t st = ds.stream;
@@ -559,16 +610,18 @@ static int msm_enqueue(spectre_gpu_ctx* ctx, DeviceState& dstate, MsmSlot& ds,
                        ds.d_lastP.ptr, nbt, acc_e, ds.d_buckets.ptr);
     timer.stamp(4);
     const uint32_t nchunks = nbt / MSM_CHUNK;
-    g1_jac* red0 = ds.d_red.ptr;
-    g1_jac* red1 = ds.d_red.ptr + nchunks;
+    g1_jac* redW = ds.d_red.ptr;
+    g1_jac* redT = redW + nchunks;
+    g1_jac* redP = redT + nchunks;  // 3 partials per window
     hipLaunchKernelGGL(k_window_chunks,
                        dim3((nchunks + THREADS - 1) / THREADS), dim3(THREADS),
-                       0, st, ds.d_buckets.ptr, nchunks, red0);
+                       0, st, ds.d_buckets.ptr, nchunks, redW, redT);
     timer.stamp(5);
-    hipLaunchKernelGGL(k_window_sum, dim3(nw), dim3(WSUM_THREADS), 0, st, red0,
-                       red1);
+    hipLaunchKernelGGL(k_window_tail, dim3(3 * nw), dim3(WSUM_THREADS), 0, st,
+                       redW, redT, redP);
     timer.stamp(6);
-    HIP_TRY(hipMemcpyAsync(ds.h_wins.ptr, red1, (size_t)nw * sizeof(g1_jac),
+    HIP_TRY(hipMemcpyAsync(ds.h_wins.ptr, redP,
+                           3 * (size_t)nw * sizeof(g1_jac),
                            hipMemcpyDeviceToHost, st));
     if (timer.on)
         HIP_TRY(hipMemcpyAsync(&timer.ent_real, ds.d_offsets.ptr + nbt, 4,
@@ -579,10 +632,23 @@ static int msm_enqueue(spectre_gpu_ctx* ctx, DeviceState& dstate, MsmSlot& ds,
     return 0;
 }
 
-// Synchronize a slot's stream and deliver the pending window sums (pinned ->
-// caller memory). Idempotent when nothing is pending. The hand-off is cleared
-// on the error returns too: a failed drain leaves neither a wedged slot nor
-// a destination that may since have been freed.
+// window = p0 + CHUNK * (p1 + LO * p2): log2(LO) + log2(CHUNK) doublings and
+// two adds (host build of g1.hpp).
+void msm_fold_window(const g1_jac& p0, const g1_jac& p1, const g1_jac& p2,
+                     g1_jac& out) {
+    g1_jac acc = p2;
+    for (uint32_t m = MSM_LO; m > 1; m >>= 1) g1j_dbl_ip(acc);
+    g1j_add_ip(acc, p1);
+    for (uint32_t m = MSM_CHUNK; m > 1; m >>= 1) g1j_dbl_ip(acc);
+    g1j_add_ip(acc, p0);
+    out = acc;
+}
+
+// Synchronize a slot's stream, fold the pending window partials (pinned) and
+// deliver the window sums (-> caller memory). Idempotent when nothing is
+// pending. The hand-off is cleared on the error returns too: a failed drain
+// leaves neither a wedged slot nor a destination that may since have been
+// freed.
 int msm_slot_drain(spectre_gpu_ctx* ctx, int dev, int slot) {
     DeviceState& dstate = ctx->devs[dev];
     if (slot < 0 || slot >= MSM_SLOTS) {
@@ -591,13 +657,21 @@ int msm_slot_drain(spectre_gpu_ctx* ctx, int dev, int slot) {
     }
     MsmSlot& sl = dstate.slots[slot];
     g1_jac* const dst = sl.pending_dst;
-    const size_t bytes = (size_t)sl.pending_n * sizeof(g1_jac);
+    const uint32_t nw = sl.pending_n;
     sl.pending_dst = nullptr;
     sl.pending_n = 0;
     HIP_TRY(hipSetDevice(dstate.device_id));
     if (sl.stream) HIP_TRY(hipStreamSynchronize(sl.stream));
     HIP_TRY(hipGetLastError());
-    if (dst) memcpy(dst, sl.h_wins.ptr, bytes);
+    if (dst) {
+        const g1_jac* p = sl.h_wins.ptr;
+        for (uint32_t w = 0; w < nw; w++, p += 3) {
+            g1_jac sum;
+            msm_fold_window(p[0], p[1], p[2], sum);
+            // caller memory of any alignment
+            memcpy((uint8_t*)dst + w * sizeof sum, &sum, sizeof sum);
+        }
+    }
     return 0;
 }
 

@@ -1,7 +1,8 @@
 """ctypes binding over libspectre_gpu.so (the product C ABI).
 
 Mirrors include/spectre_gpu.h one-to-one. Compute entry points require a
-visible AMD GPU; only `combine_partials` (host-side final reduction) and
+visible AMD GPU; only the host-side reductions (`combine_partials`,
+`combine_window_partials`, `msm_fold_window`), the pure tuning queries and
 `version` work without one — exactly the contract of the C library.
 """
 import ctypes
@@ -22,6 +23,10 @@ MSM_ACC_THREADS = 256  # bucket-accumulate workgroup size
 MSM_ACC_E_MIN = 8      # bounds of the auto entries-per-thread rule
 MSM_ACC_E_MAX = 64     # (= MSM_ACC_E_MIN / MSM_ACC_E_MAX in csrc/internal.hpp)
 MSM_ACC_TARGET_BLOCKS = 2  # accumulate blocks the rule aims at per CU
+MSM_TAIL_CHUNK = 8  # = SPECTRE_MSM_TAIL_CHUNK: buckets per reduction chunk
+MSM_TAIL_LO = 64    # = SPECTRE_MSM_TAIL_LO: columns of a window's chunk grid
+# rows of that grid: chunks per window / columns
+MSM_TAIL_HI = (1 << (WINDOW_BITS - 1)) // MSM_TAIL_CHUNK // MSM_TAIL_LO
 
 _lib = None
 
@@ -91,6 +96,10 @@ def load_library() -> ctypes.CDLL:
     lib.spectre_gpu_msm_acc_auto_entries.restype = c.c_uint32
     lib.spectre_gpu_msm_acc_auto_entries.argtypes = [
         c.c_uint64, c.c_uint32, c.c_uint32,
+    ]
+    lib.spectre_gpu_msm_fold_window.restype = c.c_int
+    lib.spectre_gpu_msm_fold_window.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
     ]
     lib.spectre_gpu_msm_g1_shard_windows_device.restype = c.c_int
     lib.spectre_gpu_msm_g1_shard_windows_device.argtypes = [
@@ -167,6 +176,21 @@ def msm_acc_auto_entries(entries: int, cus: int, resident_blocks: int) -> int:
     accumulate thread (see spectre_gpu_set_msm_acc_entries)."""
     return load_library().spectre_gpu_msm_acc_auto_entries(
         entries, cus, resident_blocks)
+
+
+def msm_fold_window(p0: bytes, p1: bytes, p2: bytes) -> bytes:
+    """Host-only: the library's fold of a window's three device partials
+    (96-byte Jacobian each) into its window sum,
+    p0 + MSM_TAIL_CHUNK * (p1 + MSM_TAIL_LO * p2)."""
+    lib = load_library()
+    assert len(p0) == len(p1) == len(p2) == 96
+    bufs = [(ctypes.c_uint8 * 96).from_buffer_copy(p) for p in (p0, p1, p2)]
+    out = (ctypes.c_uint8 * 96)()
+    rc = lib.spectre_gpu_msm_fold_window(*bufs, out)
+    if rc != 0:
+        raise RuntimeError(f"msm_fold_window failed rc={rc}: "
+                           f"{lib.spectre_gpu_last_error().decode()}")
+    return bytes(out)
 
 
 def fr_scan_tile_default() -> int:
