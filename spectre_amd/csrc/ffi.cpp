@@ -61,6 +61,10 @@ spectre_gpu_ctx* spectre_gpu_init(int device_count, const int* device_ids) {
         if (v > 0 && !(v & 3) && v <= (long)SPECTRE_MSM_ACC_ENTRIES_MAX)
             ctx->msm_acc_entries = (uint32_t)v;
     }
+    // SPECTRE_NTT_FORCE3 (any value) takes the three-axis NTT split at sizes
+    // that do not need it, where the oracle can check it; read once so the
+    // cached plans of a context all follow one rule
+    ctx->ntt_force3 = getenv("SPECTRE_NTT_FORCE3") != nullptr;
     return ctx;
 }
 

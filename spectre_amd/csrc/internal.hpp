@@ -93,12 +93,12 @@ void release_all(B&... b) {
 }
 
 struct NttPlan {
-    DevBuf<fp256> tw1;  // butterfly twiddles, axis 1
-    DevBuf<fp256> tw2;  // butterfly twiddles, axis 2
-    DevBuf<fp256> tw3;  // butterfly twiddles, axis 3 (3-pass only)
+    uint32_t npass = 0;      // axes of the split, one global pass each
+    uint32_t k[3] = {};      // log2 axis sizes; the last is the contiguous one
+    DevBuf<fp256> tw[3];     // butterfly twiddles per axis, 2^(k-1) entries
     DevBuf<fp256> twB;  // T1 || T2 omega-power lookup (w^e = T1[e&fff]*T2[e>>12])
-    uint32_t k1 = 0, k2 = 0, k3 = 0;
-    void release() { release_all(tw1, tw2, tw3, twB); }
+    uint32_t t1n = 0;        // entries of T1
+    void release() { release_all(tw[0], tw[1], tw[2], twB); }
 };
 
 // Per-slot MSM pipeline state: MSM_SLOTS slots per device let call i+1's
@@ -169,7 +169,7 @@ struct DeviceState {
     // total in the last slot), and the pinned landing spot of that total ----
     DevBuf<fp256> d_gp_prods;
     PinnedBuf<fp256> h_gp_last;
-    std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n||inverse
+    std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n
     // frees everything this device owns; the caller has made it current
     void release() {
         for (auto& sl : slots) sl.release(stream);
@@ -193,6 +193,7 @@ struct spectre_gpu_ctx {
     std::recursive_mutex mu;
     uint32_t msm_acc_entries = 0;  // entries per accumulate thread, 0 = auto
     uint32_t fr_scan_tile = 0;     // elements per poly.hip tile, 0 = default
+    bool ntt_force3 = false;       // three-axis NTT split at every log_n >= 3
 };
 
 // One MSM pipeline run: nbatch scalar vectors (batch-major, nbatch*n*32 B)
@@ -235,7 +236,7 @@ int msm_slot_drain(spectre_gpu_ctx* ctx, int dev, int slot);
 void msm_fold_window(const g1_jac& p0, const g1_jac& p1, const g1_jac& p2,
                      g1_jac& out);
 
-// ntt.hip — gate-expression evaluator over device column buffers
+// gate.hip — gate-expression evaluator over device column buffers
 // (synchronizes). cols = host array of ncols device pointers.
 int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
                         const fp256* const* cols, uint32_t ncols,
@@ -243,7 +244,7 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
                         const uint32_t* program, uint32_t nops, uint64_t n,
                         uint32_t rot_scale, const fp256* y, fp256* d_out);
 
-// ntt.hip — pointwise Fr vector op on device buffers (synchronizes).
+// gate.hip — pointwise Fr vector op on device buffers (synchronizes).
 int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                      const fp256* d_b, const fp256* c, fp256* d_out,
                      uint64_t n);

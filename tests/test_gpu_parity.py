@@ -523,9 +523,11 @@ def test_error_paths(gpu):
         gpu.msm_batch(b"\x00" * 64, b"\x00" * (33 * 32), 33, 1)
 
 
-def test_ntt_three_pass_forced_vs_oracle(oracle, golden):
-    """The 3-pass (log_n>24) path, forced at oracle-checkable sizes via
-    SPECTRE_NTT_FORCE3, must match the oracle bit-exactly (fwd/inv/coset)."""
+def _ntt_legs_vs_oracle_in_child(env, log_ns):
+    """In a fresh child process (the split rule is fixed when the context is
+    created) under `env` on top of the caller's environment minus
+    SPECTRE_NTT_FORCE3: forward, inverse, forward-coset and inverse-coset
+    NTT of every log_n must match the oracle bit-exactly."""
     import os
     import subprocess
     import sys
@@ -540,7 +542,8 @@ fix = json.load(open(os.path.join(%r, "tests", "golden", "ntt.json")))
 w12 = bytes.fromhex([c for c in fix["seeded_cases"] if c["log_n"] == 12][0]["omega_mont"])
 gpu = SpectreGpu([0])
 g = oracle.fr_from_canonical((5).to_bytes(32, "little"))
-for log_n in (6, 10, 12, 14):
+gi = oracle.fr_inv(g)
+for log_n in %r:
     w = w12
     if log_n <= 12:
         for _ in range(12 - log_n):
@@ -556,12 +559,32 @@ for log_n in (6, 10, 12, 14):
     wi = oracle.fr_inv(w)
     assert gpu.ntt(a, log_n, wi, inverse=True) == oracle.ntt(a, log_n, wi, inverse=True), log_n
     assert gpu.ntt(a, log_n, w, coset_gen=g) == oracle.ntt(a, log_n, w, coset_gen=g), log_n
-print("force3 ok")
-''' % (REPO, REPO + "/oracle", REPO)
-    env = dict(os.environ, SPECTRE_NTT_FORCE3="1")
-    r = subprocess.run([sys.executable, "-c", code], env=env,
+    assert (gpu.ntt(a, log_n, wi, inverse=True, coset_gen=gi)
+            == oracle.ntt(a, log_n, wi, inverse=True, coset_gen=gi)), log_n
+print("ntt legs ok")
+''' % (REPO, REPO + "/oracle", REPO, tuple(log_ns))
+    child_env = {k: v for k, v in os.environ.items()
+                 if k != "SPECTRE_NTT_FORCE3"}
+    child_env.update(env)
+    r = subprocess.run([sys.executable, "-c", code], env=child_env,
                        capture_output=True, text=True, timeout=300)
-    assert "force3 ok" in r.stdout, r.stdout + r.stderr
+    assert "ntt legs ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_ntt_three_pass_forced_vs_oracle(oracle, golden):
+    """The 3-pass (log_n>24) path, forced at oracle-checkable sizes via
+    SPECTRE_NTT_FORCE3, must match the oracle bit-exactly (fwd/inv/coset,
+    and the inverse coset on the scattered store). log_n 3, 4, 5, 7 split
+    (1,1,1), (2,1,1), (2,2,1), (3,2,2): one-entry twiddle tables and unequal
+    axes."""
+    _ntt_legs_vs_oracle_in_child({"SPECTRE_NTT_FORCE3": "1"},
+                                 (3, 4, 5, 7, 6, 10, 12, 14))
+
+
+def test_ntt_two_pass_short_first_axis_vs_oracle(oracle, golden):
+    """The default rule's (1,12) and (2,12) splits at log_n 13 and 14: a
+    one- and a two-entry twiddle table on the strided pass, all four legs."""
+    _ntt_legs_vs_oracle_in_child({}, (13, 14))
 
 
 def test_ntt_2pow25_roundtrip(gpu, oracle, golden):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """NTT timing probe (GPU box): device-resident forward/inverse/coset NTT at
 the BASELINE sizes. Not part of the bench contract — a tuning tool."""
+import argparse
+import hashlib
 import os
 import sys
 import time
@@ -23,23 +25,44 @@ def omega_for(log_n):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("sizes", nargs="*", type=int, default=[20, 22, 23, 24],
+                    metavar="LOG_N")
+    ap.add_argument("--reps", default="10",
+                    help="calls per timed window: one count, or one per "
+                         "size separated by commas (default 10)")
+    ap.add_argument("--hash", action="store_true",
+                    help="also print the sha256 of the downloaded output of "
+                         "one forward, one inverse and one coset call per "
+                         "size, each on the freshly uploaded input")
+    args = ap.parse_args()
+    reps_list = [int(r) for r in args.reps.split(",")]
+    if len(reps_list) == 1:
+        reps_list *= len(args.sizes)
+    if len(reps_list) != len(args.sizes) or min(reps_list) < 1:
+        ap.error("--reps wants one positive count, or one per size")
+
     gpu = SpectreGpu([0])
     g = oracle.fr_from_canonical((5).to_bytes(32, "little"))
-    sizes = ([int(a) for a in sys.argv[1:]] if len(sys.argv) > 1
-             else [20, 22, 23, 24])
-    for log_n in sizes:
+    for log_n, reps in zip(args.sizes, reps_list):
         n = 1 << log_n
         data = oracle.gen_fr_vector(min(n, 1 << 20), 7)
         data = data * (n // (1 << min(log_n, 20)))
         w = omega_for(log_n)
         wi = oracle.fr_inv(w)
+        legs = [("fwd", dict()), ("inv", dict(inverse=True)),
+                ("coset", dict(coset_gen=g))]
         d = gpu.malloc(32 * n)
+        if args.hash:
+            for name, kw in legs:
+                gpu.upload(d, data)
+                gpu.ntt_device(d, log_n, wi if kw.get("inverse") else w, **kw)
+                h = hashlib.sha256(gpu.download(d, 32 * n)).hexdigest()
+                print(f"2^{log_n} {name} sha256 {h}")
         gpu.upload(d, data)
         gpu.ntt_device(d, log_n, w)  # warm (plan build)
         gpu.ntt_device(d, log_n, wi, inverse=True)
-        reps = 10
-        for name, kw in [("fwd", dict()), ("inv", dict(inverse=True)),
-                         ("coset", dict(coset_gen=g))]:
+        for name, kw in legs:
             om = wi if kw.get("inverse") else w
             t0 = time.time()
             for _ in range(reps):
@@ -47,7 +70,8 @@ def main():
             dt = (time.time() - t0) / reps * 1e3
             gb = 2 * n * 32 / 1e9  # algorithmic: one read+write per pass pair
             print(f"2^{log_n} {name}: {dt:7.3f} ms  "
-                  f"({2 * gb / dt * 1e3:7.1f} GB/s algorithmic 2-pass)")
+                  f"({2 * gb / dt * 1e3:7.1f} GB/s algorithmic 2-pass)"
+                  f"  x{reps}")
         gpu.free(d)
     gpu.close()
 
