@@ -31,7 +31,10 @@ struct fp256 {
 // ---- constant providers -----------------------------------------------------
 // Constants derived from the published alt_bn128 moduli (values verified
 // against tests/golden fixtures; see tests/golden/bn254_ref.py).
+// kAsmMul: which multiply ff_mul<C> is in device code, the asm column form
+// (true) or the compiled CIOS (false). The host always runs the CIOS.
 struct FqP {
+    static constexpr bool kAsmMul = true;
     FF_HD static constexpr uint32_t mod(int i) {
         constexpr uint32_t M[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
                                    0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
@@ -50,6 +53,7 @@ struct FqP {
     }
 };
 struct FrP {
+    static constexpr bool kAsmMul = true;
     FF_HD static constexpr uint32_t mod(int i) {
         constexpr uint32_t M[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u,
                                    0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
@@ -66,6 +70,11 @@ struct FrP {
                                    0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};
         return M[i];
     }
+};
+// Fr with the compiled CIOS multiply on the device too, for the kernels that
+// measured faster with it (ntt.hip, gate.hip).
+struct FrCios : FrP {
+    static constexpr bool kAsmMul = false;
 };
 
 // ---- generic ops ------------------------------------------------------------
@@ -140,11 +149,10 @@ template <class C> FF_HD void ff_neg(fp256& o, const fp256& a) {
     for (int i = 0; i < 8; i++) m.l[i] = C::mod(i);
     ff_sub_raw(o, m, a);
 }
-FF_HD void ff_dbl_raw(fp256& o, const fp256& a) { ff_add_raw(o, a, a); }
 
-// CIOS Montgomery multiplication, 8x32 limbs, 64-bit accumulators.
-// (Host path + reference; the device path below dispatches to the asm
-// column form, which must stay bit-identical to this.)
+// CIOS Montgomery multiplication, 8x32 limbs, 64-bit accumulators: the host
+// multiply, and the device multiply of the fields with kAsmMul == false. The
+// asm column form below must stay bit-identical to this.
 template <class C> FF_HD void ff_mul_cios(fp256& o, const fp256& a, const fp256& b) {
     uint32_t t[10];
     for (int i = 0; i < 10; i++) t[i] = 0;
@@ -177,13 +185,14 @@ template <class C> FF_HD void ff_mul_cios(fp256& o, const fp256& a, const fp256&
 // ---- device multiply: hand-scheduled column Montgomery --------------------
 // On gfx950 the asm column form runs at ~135 G Fq-mul/s vs ~103 for the
 // compiled CIOS (measured, tools/microbench.hip) and is bit-identical
-// (256K-lane chained check + the whole GPU parity suite). Define
-// SPECTRE_NO_ASM_MUL to fall back to the C form for debugging/A-B.
+// (256K-lane chained check + the whole GPU parity suite). A field takes it
+// through C::kAsmMul; building everything with -DSPECTRE_NO_ASM_MUL turns it
+// off for every field (debugging / A-B).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SPECTRE_NO_ASM_MUL)
-#define FF_USE_ASM_MUL 1
+#define FF_HAVE_ASM_MUL 1
 #endif
 
-#if defined(FF_USE_ASM_MUL)
+#if defined(FF_HAVE_ASM_MUL)
 // Single product: acc += a*b (64-bit mad), ovf += carry-out. Explicit
 // carry-mask pairs ("=s"): a vcc clobber makes hipcc pad every block
 // boundary with s_nop hazards.
@@ -250,8 +259,8 @@ __device__ __forceinline__ void detail_ff_high_cols(uint64_t& acc,
 // complete, high columns emit the result; ovf counts 64-bit carry-outs per
 // column (<= 16 products). Result < 2p, one conditional subtract.
 template <class C>
-__device__ __forceinline__ void ff_mul(fp256& o, const fp256& A,
-                                       const fp256& B) {
+__device__ __forceinline__ void ff_mul_cols(fp256& o, const fp256& A,
+                                            const fp256& B) {
     uint32_t m[8];
     uint64_t acc = 0;
     uint32_t ovf = 0;
@@ -263,11 +272,18 @@ __device__ __forceinline__ void ff_mul(fp256& o, const fp256& A,
     // rather than truncating silently.
     ff_cond_sub_mod<C>(o, (uint32_t)(acc >> 32));
 }
-#else
+#endif
+
+// The one multiply: the form the field names on the device, CIOS on the host.
 template <class C> FF_HD void ff_mul(fp256& o, const fp256& a, const fp256& b) {
+#if defined(FF_HAVE_ASM_MUL)
+    if constexpr (C::kAsmMul) {
+        ff_mul_cols<C>(o, a, b);
+        return;
+    }
+#endif
     ff_mul_cios<C>(o, a, b);
 }
-#endif
 
 template <class C> FF_HD void ff_sqr(fp256& o, const fp256& a) { ff_mul<C>(o, a, a); }
 
@@ -284,16 +300,6 @@ template <class C> FF_HD void ff_from_mont(fp256& o, const fp256& a) {
     ff_mul<C>(o, a, one);
 }
 
-// a^e, e a canonical 256-bit little-endian exponent; a, out Montgomery.
-template <class C> FF_HD void ff_pow(fp256& o, const fp256& a, const fp256& e) {
-    fp256 acc, base = a;
-    ff_set_one<C>(acc);
-    for (int i = 0; i < 256; i++) {
-        if ((e.l[i >> 5] >> (i & 31)) & 1) ff_mul<C>(acc, acc, base);
-        ff_sqr<C>(base, base);
-    }
-    o = acc;
-}
 // a^e for small 32-bit exponent (twiddle powers)
 template <class C> FF_HD void ff_pow_u32(fp256& o, const fp256& a, uint32_t e) {
     fp256 acc, base = a;
@@ -305,20 +311,26 @@ template <class C> FF_HD void ff_pow_u32(fp256& o, const fp256& a, uint32_t e) {
     }
     o = acc;
 }
-// Fermat inverse: a^(m-2)
+// Fermat inverse a^(m-2), square-and-multiply over the exponent's 8 words.
+// The words are selected by compares, not read from a local array, which the
+// device compiler would place in scratch memory; the loops stay rolled. In a
+// kernel every branch is uniform when the wave inverts one value.
 template <class C> FF_HD void ff_inv(fp256& o, const fp256& a) {
-    fp256 e;
-    for (int i = 0; i < 8; i++) e.l[i] = C::mod(i);
-    // subtract 2 (low limb of both moduli is odd and >= 2^0+...; handle borrow anyway)
-    uint64_t d = (uint64_t)e.l[0] - 2;
-    e.l[0] = (uint32_t)d;
-    uint64_t brw = (d >> 32) & 1;
-    for (int i = 1; i < 8 && brw; i++) {
-        d = (uint64_t)e.l[i] - brw;
-        e.l[i] = (uint32_t)d;
-        brw = (d >> 32) & 1;
+    static_assert(C::mod(0) >= 2u, "m - 2 must not borrow out of the low word");
+    fp256 acc, base = a;
+    ff_set_one<C>(acc);
+#pragma unroll 1
+    for (uint32_t w = 0; w < 8; w++) {
+        uint32_t bits = C::mod(0) - 2u;
+#pragma unroll
+        for (uint32_t i = 1; i < 8; i++) bits = w == i ? C::mod(i) : bits;
+#pragma unroll 1
+        for (uint32_t b = 0; b < 32; b++) {
+            if ((bits >> b) & 1) ff_mul<C>(acc, acc, base);
+            ff_sqr<C>(base, base);
+        }
     }
-    ff_pow<C>(o, a, e);
+    o = acc;
 }
 
 FF_HD void ff_from_bytes(fp256& o, const uint8_t* b) { memcpy(o.l, b, 32); }
@@ -326,3 +338,27 @@ FF_HD void ff_to_bytes(uint8_t* b, const fp256& a) { memcpy(b, a.l, 32); }
 
 using Fq = FqP;
 using Fr = FrP;
+
+// ---- split LDS element ------------------------------------------------------
+// A 32-B element kept whole in LDS spans 8 banks, so power-of-two strides
+// conflict. The kernels store it as two 16-B halves, the low one at lds4[lo]
+// and the high one `dist` entries further on: consecutive elements then
+// stride 4 banks. The caller owns the layout (lo and dist). The sum is written
+// dist + lo, the order under which k_ntt_pass was measured (the other order
+// compiles to different code, profiles/field_layer_text_identity.txt).
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void lds_split_ld(const uint4* lds4, uint32_t lo,
+                                             uint32_t dist, fp256& o) {
+    uint4 l = lds4[lo], h = lds4[dist + lo];
+    memcpy(&o.l[0], &l, 16);
+    memcpy(&o.l[4], &h, 16);
+}
+__device__ __forceinline__ void lds_split_st(uint4* lds4, uint32_t lo,
+                                             uint32_t dist, const fp256& v) {
+    uint4 l, h;
+    memcpy(&l, &v.l[0], 16);
+    memcpy(&h, &v.l[4], 16);
+    lds4[lo] = l;
+    lds4[dist + lo] = h;
+}
+#endif

@@ -195,13 +195,9 @@ static void winsums_to_affine(const g1_jac* wins, uint8_t out[64]) {
     g1j_set_inf(res);
     for (int w = MSM_NWIN - 1; w >= 0; w--) {
         if (w != MSM_NWIN - 1) {
-            for (int d = 0; d < MSM_WBITS; d++) {
-                g1_jac t = res;
-                g1j_dbl(res, t);
-            }
+            for (int d = 0; d < MSM_WBITS; d++) g1j_dbl_ip(res);
         }
-        g1_jac t = res;
-        g1j_add(res, t, wins[w]);
+        g1j_add_ip(res, wins[w]);
     }
     g1_affine a;
     g1j_to_affine(a, res);
@@ -219,10 +215,7 @@ int spectre_gpu_msm_g1_combine(const uint8_t* partials, uint32_t nshards,
     for (int w = 0; w < MSM_NWIN; w++) g1j_set_inf(tot[w]);
     for (uint32_t s = 0; s < nshards; s++) {  // deterministic rank order
         const g1_jac* sh = (const g1_jac*)(partials + (size_t)s * MSM_NWIN * 96);
-        for (int w = 0; w < MSM_NWIN; w++) {
-            g1_jac t = tot[w];
-            g1j_add(tot[w], t, sh[w]);
-        }
+        for (int w = 0; w < MSM_NWIN; w++) g1j_add_ip(tot[w], sh[w]);
     }
     winsums_to_affine(tot, out_affine);
     return 0;

@@ -1,10 +1,12 @@
 // gate.hip — quotient-phase glue over Fr: the gate-expression evaluator and
 // the pointwise vector ops.
 //
-// Both kernels are compiled with the C CIOS multiply, the choice they were
-// written and measured under; neither has been timed with the asm multiply.
-#define SPECTRE_NO_ASM_MUL 1
+// Both kernels compute in GateFr, Fr with the C CIOS multiply, the choice they
+// were written and measured under; neither has been timed with the asm
+// multiply.
 #include "internal.hpp"
+
+using GateFr = FrCios;
 
 #define THREADS 256  // vector op
 
@@ -28,6 +30,9 @@ __global__ __launch_bounds__(GATE_THREADS) void k_fr_gate_eval(
     fp256 tos;
     ff_set_zero(tos);
     int depth = 0;
+    // Same split as lds_split_ld / lds_split_st (ff.hpp), written out: with
+    // the high half addressed as low + T the compiler emits other address
+    // arithmetic for this kernel, and that has not been measured.
     auto lds_slot_st = [&](int s, const fp256& v) {
         uint4 lo, hi;
         memcpy(&lo, &v.l[0], 16);
@@ -57,20 +62,20 @@ __global__ __launch_bounds__(GATE_THREADS) void k_fr_gate_eval(
             }
             depth++;
         } else if (op == SPECTRE_GATE_OP_NEG) {
-            ff_neg<Fr>(tos, tos);
+            ff_neg<GateFr>(tos, tos);
         } else {  // binary: (second) op (top)
             fp256 lhs;
             lds_slot_ld(depth - 2, lhs);
-            if (op == SPECTRE_GATE_OP_ADD) ff_add<Fr>(tos, lhs, tos);
-            else if (op == SPECTRE_GATE_OP_SUB) ff_sub<Fr>(tos, lhs, tos);
-            else ff_mul<Fr>(tos, lhs, tos);
+            if (op == SPECTRE_GATE_OP_ADD) ff_add<GateFr>(tos, lhs, tos);
+            else if (op == SPECTRE_GATE_OP_SUB) ff_sub<GateFr>(tos, lhs, tos);
+            else ff_mul<GateFr>(tos, lhs, tos);
             depth--;
         }
     }
     if (use_y) {
         fp256 acc = out[row];
-        ff_mul<Fr>(acc, acc, y);
-        ff_add<Fr>(tos, acc, tos);
+        ff_mul<GateFr>(acc, acc, y);
+        ff_add<GateFr>(tos, acc, tos);
     }
     out[row] = tos;
 }
@@ -169,14 +174,14 @@ __global__ void k_fr_vec_op(int op, const fp256* __restrict__ a,
     if (i >= n) return;
     fp256 r, va = a[i];
     switch (op) {
-        case SPECTRE_VEC_ADD: ff_add<Fr>(r, va, b[i]); break;
-        case SPECTRE_VEC_SUB: ff_sub<Fr>(r, va, b[i]); break;
-        case SPECTRE_VEC_MUL: ff_mul<Fr>(r, va, b[i]); break;
-        case SPECTRE_VEC_SCALE: ff_mul<Fr>(r, va, c); break;
+        case SPECTRE_VEC_ADD: ff_add<GateFr>(r, va, b[i]); break;
+        case SPECTRE_VEC_SUB: ff_sub<GateFr>(r, va, b[i]); break;
+        case SPECTRE_VEC_MUL: ff_mul<GateFr>(r, va, b[i]); break;
+        case SPECTRE_VEC_SCALE: ff_mul<GateFr>(r, va, c); break;
         default: {  // ADD_SCALED
             fp256 t;
-            ff_mul<Fr>(t, b[i], c);
-            ff_add<Fr>(r, va, t);
+            ff_mul<GateFr>(t, b[i], c);
+            ff_add<GateFr>(r, va, t);
         }
     }
     out[i] = r;

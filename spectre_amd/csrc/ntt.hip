@@ -39,14 +39,17 @@
 // All Fr math is 8x32-limb Montgomery (ff.hpp); data stays in Montgomery form
 // end-to-end exactly as halo2 holds its &[Fr] slices.
 //
-// This TU keeps the C CIOS multiply: the asm column multiply regressed the
-// 1024-thread LDS kernels ~7% (2^23 fwd 2.59 -> 2.77 ms — register pressure
-// at the 4-waves/SIMD occupancy these kernels need), while it wins ~28% in
-// the 256-thread MSM kernels. Per-TU choice, measured r2.
-#ifndef SPECTRE_NTT_ASMMUL  // variant: -DSPECTRE_NTT_ASMMUL re-tests the
-#define SPECTRE_NO_ASM_MUL 1  // asm multiply under new block geometries
-#endif
+// This file computes in NttFr, Fr with the C CIOS multiply: the asm column
+// multiply regressed the 1024-thread LDS kernels ~7% (2^23 fwd 2.59 -> 2.77
+// ms — register pressure at the 4-waves/SIMD occupancy these kernels need),
+// while it wins ~28% in the 256-thread MSM kernels. Measured r2.
 #include "internal.hpp"
+
+#ifdef SPECTRE_NTT_ASMMUL  // variant: re-tests the asm multiply under new
+using NttFr = Fr;          // block geometries
+#else
+using NttFr = FrCios;
+#endif
 
 #define THREADS 256       // pow-table builder
 #define NTT_THREADS 1024  // NTT passes: 16 waves/block so one LDS-resident
@@ -61,27 +64,13 @@ __device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t bits) {
 // covers only 8 bank-octets — inherent 2-8x conflict at power-of-two
 // butterfly strides (measured SQ_LDS_BANK_CONFLICT/IDX_ACTIVE = 0.85 with a
 // single fp256 array). Instead each element is stored as TWO 16-B halves in
-// separate regions (lo at [i], hi at [H+i]): consecutive elements stride 4
-// banks and one lane group covers all 64 banks.
+// separate regions (lo at [i], hi at [H+i]; lds_split_ld / lds_split_st):
+// consecutive elements stride 4 banks and one lane group covers all 64 banks.
 #define LDS_BYTES(L) ((uint32_t)(L) * 32u)
-__device__ __forceinline__ void lds_ld(const uint4* lds4, uint32_t H,
-                                       uint32_t i, fp256& o) {
-    uint4 lo = lds4[i], hi = lds4[H + i];
-    memcpy(&o.l[0], &lo, 16);
-    memcpy(&o.l[4], &hi, 16);
-}
-__device__ __forceinline__ void lds_st(uint4* lds4, uint32_t H, uint32_t i,
-                                       const fp256& v) {
-    uint4 lo, hi;
-    memcpy(&lo, &v.l[0], 16);
-    memcpy(&hi, &v.l[4], 16);
-    lds4[i] = lo;
-    lds4[H + i] = hi;
-}
 // g^e via the 2D power table (e < n)
 __device__ __forceinline__ void tw_lookup(fp256& o, const fp256* T1,
                                           const fp256* T2, uint32_t e) {
-    ff_mul<Fr>(o, T1[e & TW_LOW_MASK], T2[e >> TW_LOW_BITS]);
+    ff_mul<NttFr>(o, T1[e & TW_LOW_MASK], T2[e >> TW_LOW_BITS]);
 }
 
 // out[j] = base^j, j < count
@@ -90,7 +79,7 @@ __global__ void k_pow_table(fp256 base, fp256* __restrict__ out,
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= count) return;
     fp256 v;
-    ff_pow_u32<Fr>(v, base, j);
+    ff_pow_u32<NttFr>(v, base, j);
     out[j] = v;
 }
 
@@ -120,13 +109,13 @@ __device__ void lds_dif(uint4* lds4, uint32_t H, const fp256* __restrict__ twL,
                 uint32_t blk = p / h, j = p % h;
                 uint32_t i0 = blk * 2 * h + j, i1 = i0 + h;
                 fp256 u, v, t, w;
-                lds_ld(lds4, H, i0, u);
-                lds_ld(lds4, H, i1, v);
-                ff_add<Fr>(w, u, v);
-                lds_st(lds4, H, i0, w);
-                ff_sub<Fr>(t, u, v);
-                ff_mul<Fr>(t, t, twL[(uint64_t)j * stride]);
-                lds_st(lds4, H, i1, t);
+                lds_split_ld(lds4, i0, H, u);
+                lds_split_ld(lds4, i1, H, v);
+                ff_add<NttFr>(w, u, v);
+                lds_split_st(lds4, i0, H, w);
+                ff_sub<NttFr>(t, u, v);
+                ff_mul<NttFr>(t, t, twL[(uint64_t)j * stride]);
+                lds_split_st(lds4, i1, H, t);
             }
             __syncthreads();
             if constexpr (R4) { h >>= 1; break; }
@@ -140,30 +129,30 @@ __device__ void lds_dif(uint4* lds4, uint32_t H, const fp256* __restrict__ twL,
             const uint32_t blk = p / hh, j = p % hh;
             const uint32_t i0 = blk * 2 * h + j;
             fp256 a, b, c, d, t;
-            lds_ld(lds4, H, i0, a);
-            lds_ld(lds4, H, i0 + hh, b);
-            lds_ld(lds4, H, i0 + h, c);
-            lds_ld(lds4, H, i0 + h + hh, d);
+            lds_split_ld(lds4, i0, H, a);
+            lds_split_ld(lds4, i0 + hh, H, b);
+            lds_split_ld(lds4, i0 + h, H, c);
+            lds_split_ld(lds4, i0 + h + hh, H, d);
             // level h: pairs (a,c) at offset j and (b,d) at offset j+hh
             fp256 a1, b1, c1, d1;
-            ff_add<Fr>(a1, a, c);
-            ff_sub<Fr>(t, a, c);
-            ff_mul<Fr>(c1, t, twL[(uint64_t)j * s_h]);
-            ff_add<Fr>(b1, b, d);
-            ff_sub<Fr>(t, b, d);
-            ff_mul<Fr>(d1, t, twL[(uint64_t)(j + hh) * s_h]);
+            ff_add<NttFr>(a1, a, c);
+            ff_sub<NttFr>(t, a, c);
+            ff_mul<NttFr>(c1, t, twL[(uint64_t)j * s_h]);
+            ff_add<NttFr>(b1, b, d);
+            ff_sub<NttFr>(t, b, d);
+            ff_mul<NttFr>(d1, t, twL[(uint64_t)(j + hh) * s_h]);
             // level h/2: pairs (a1,b1) and (c1,d1), both at offset j,
             // twiddle stride 2*s_h
-            ff_add<Fr>(a, a1, b1);
-            ff_sub<Fr>(t, a1, b1);
-            ff_mul<Fr>(b, t, twL[(uint64_t)j * 2 * s_h]);
-            ff_add<Fr>(c, c1, d1);
-            ff_sub<Fr>(t, c1, d1);
-            ff_mul<Fr>(d, t, twL[(uint64_t)j * 2 * s_h]);
-            lds_st(lds4, H, i0, a);
-            lds_st(lds4, H, i0 + hh, b);
-            lds_st(lds4, H, i0 + h, c);
-            lds_st(lds4, H, i0 + h + hh, d);
+            ff_add<NttFr>(a, a1, b1);
+            ff_sub<NttFr>(t, a1, b1);
+            ff_mul<NttFr>(b, t, twL[(uint64_t)j * 2 * s_h]);
+            ff_add<NttFr>(c, c1, d1);
+            ff_sub<NttFr>(t, c1, d1);
+            ff_mul<NttFr>(d, t, twL[(uint64_t)j * 2 * s_h]);
+            lds_split_st(lds4, i0, H, a);
+            lds_split_st(lds4, i0 + hh, H, b);
+            lds_split_st(lds4, i0 + h, H, c);
+            lds_split_st(lds4, i0 + h + hh, H, d);
         }
         __syncthreads();
     }
@@ -205,30 +194,30 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(NttPass p) {
         if (p.cT1 && !p.inverse) {  // forward coset: g^(original index)
             fp256 f;
             tw_lookup(f, p.cT1, p.cT2, (uint32_t)pos);
-            ff_mul<Fr>(v, v, f);
+            ff_mul<NttFr>(v, v, f);
         }
-        lds_st(lds4, H, s, v);
+        lds_split_st(lds4, s, H, v);
     }
     __syncthreads();
     lds_dif<R4>(lds4, H, p.twL, p.logL);
     for (uint32_t s = threadIdx.x; s < L; s += blockDim.x) {
         const uint32_t t = bitrev(s, p.logL);
         fp256 v, f;
-        lds_ld(lds4, H, s, v);
+        lds_split_ld(lds4, s, H, v);
         uint64_t opos;
         if (!p.last) {
             tw_lookup(f, p.T1, p.T2, (t << p.tw_shift) * mS);
-            ff_mul<Fr>(v, v, f);
+            ff_mul<NttFr>(v, v, f);
             opos = base + ((uint64_t)t << p.logS);
         } else {
-            if (p.inverse) ff_mul<Fr>(v, v, p.scale);
+            if (p.inverse) ff_mul<NttFr>(v, v, p.scale);
             const uint32_t tA = m >> p.fin_logB;
             const uint32_t tB = m & ((1u << p.fin_logB) - 1);
             opos = (uint64_t)tA + ((uint64_t)tB << p.fin_logA) +
                    ((uint64_t)t << (p.fin_logA + p.fin_logB));
             if (p.cT1 && p.inverse) {  // inverse coset: g^(output index)
                 tw_lookup(f, p.cT1, p.cT2, (uint32_t)opos);
-                ff_mul<Fr>(v, v, f);
+                ff_mul<NttFr>(v, v, f);
             }
         }
         p.out[opos] = v;
@@ -283,7 +272,7 @@ static int build_lookup_tables(DeviceState& ds, const fp256& g, uint32_t n,
     const uint32_t t2n = n / t1n;
     RC_TRY(buf.reserve((size_t)t1n + t2n));
     fp256 gT2;
-    ff_pow_u32<Fr>(gT2, g, 1u << TW_LOW_BITS);
+    ff_pow_u32<NttFr>(gT2, g, 1u << TW_LOW_BITS);
     build_table(ds, g, buf.ptr, t1n);
     build_table(ds, gT2, buf.ptr + t1n, t2n);
     return 0;
@@ -297,7 +286,7 @@ static int build_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
     RC_TRY(build_lookup_tables(ds, omega, 1u << log_n, p.t1n, p.twB));
     for (uint32_t i = 0; i < p.npass; i++) {
         fp256 root;  // of axis i's DFT
-        ff_pow_u32<Fr>(root, omega, 1u << (log_n - p.k[i]));
+        ff_pow_u32<NttFr>(root, omega, 1u << (log_n - p.k[i]));
         const uint32_t half = 1u << (p.k[i] - 1);
         RC_TRY(p.tw[i].reserve(half));
         build_table(ds, root, p.tw[i].ptr, half);
@@ -367,8 +356,8 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
         fp256 ncanon, nm;
         ff_set_zero(ncanon);
         ncanon.l[log_n >> 5] = 1u << (log_n & 31);
-        ff_to_mont<Fr>(nm, ncanon);
-        ff_inv<Fr>(pass.scale, nm);
+        ff_to_mont<NttFr>(nm, ncanon);
+        ff_inv<NttFr>(pass.scale, nm);
     }
     // data -> tmp, tmp in place, tmp -> data; a single pass runs on data
     uint32_t done = 0;  // log sizes of the axes already transformed

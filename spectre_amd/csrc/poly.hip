@@ -38,24 +38,9 @@
 #define POLY_TILE_DEFAULT (POLY_THREADS * POLY_E_MAX)
 #define POLY_MAX_N (1ull << 28)
 // tree nodes 1 .. 2*POLY_THREADS-1, bank-split as in ntt.hip: the low 16 B of
-// node i at lds4[i], the high 16 B at lds4[POLY_H + i], so consecutive nodes
-// stride 4 banks instead of 8.
+// node i at lds4[i], the high 16 B at lds4[POLY_H + i] (lds_split_ld /
+// lds_split_st), so consecutive nodes stride 4 banks instead of 8.
 #define POLY_H (2 * POLY_THREADS)
-
-__device__ __forceinline__ void tree_ld(const uint4* lds4, uint32_t i,
-                                        fp256& o) {
-    uint4 lo = lds4[i], hi = lds4[POLY_H + i];
-    memcpy(&o.l[0], &lo, 16);
-    memcpy(&o.l[4], &hi, 16);
-}
-__device__ __forceinline__ void tree_st(uint4* lds4, uint32_t i,
-                                        const fp256& v) {
-    uint4 lo, hi;
-    memcpy(&lo, &v.l[0], 16);
-    memcpy(&hi, &v.l[4], 16);
-    lds4[i] = lo;
-    lds4[POLY_H + i] = hi;
-}
 
 // leaves <- v, then the up-sweep. On return (after its last barrier) node 1
 // holds the product of all leaves. The leading barrier lets a caller reuse
@@ -63,15 +48,15 @@ __device__ __forceinline__ void tree_st(uint4* lds4, uint32_t i,
 __device__ __forceinline__ void tree_up(uint4* lds4, uint32_t t,
                                         const fp256& v) {
     __syncthreads();
-    tree_st(lds4, POLY_THREADS + t, v);
+    lds_split_st(lds4, POLY_THREADS + t, POLY_H, v);
     __syncthreads();
     for (uint32_t w = POLY_THREADS / 2; w >= 1; w >>= 1) {
         if (t < w) {
             fp256 a, b, c;
-            tree_ld(lds4, 2 * (w + t), a);
-            tree_ld(lds4, 2 * (w + t) + 1, b);
+            lds_split_ld(lds4, 2 * (w + t), POLY_H, a);
+            lds_split_ld(lds4, 2 * (w + t) + 1, POLY_H, b);
             ff_mul<Fr>(c, a, b);
-            tree_st(lds4, w + t, c);
+            lds_split_st(lds4, w + t, POLY_H, c);
         }
         __syncthreads();
     }
@@ -87,44 +72,20 @@ __device__ __forceinline__ void tree_down(uint4* lds4, uint32_t t) {
         if (t < w) {
             const uint32_t i = w + t;
             fp256 x, l, r, o;
-            tree_ld(lds4, i, x);
-            tree_ld(lds4, 2 * i, l);
+            lds_split_ld(lds4, i, POLY_H, x);
+            lds_split_ld(lds4, 2 * i, POLY_H, l);
             if (kInvert) {
-                tree_ld(lds4, 2 * i + 1, r);
+                lds_split_ld(lds4, 2 * i + 1, POLY_H, r);
                 ff_mul<Fr>(o, x, r);
-                tree_st(lds4, 2 * i, o);
+                lds_split_st(lds4, 2 * i, POLY_H, o);
             } else {
-                tree_st(lds4, 2 * i, x);
+                lds_split_st(lds4, 2 * i, POLY_H, x);
             }
             ff_mul<Fr>(o, x, l);
-            tree_st(lds4, 2 * i + 1, o);
+            lds_split_st(lds4, 2 * i + 1, POLY_H, o);
         }
         __syncthreads();
     }
-}
-
-// a^(r-2): ff_inv<Fr>'s square-and-multiply chain with the exponent's words
-// selected by compares instead of indexing a local array, which the device
-// compiler would place in scratch memory. Every branch is wave-uniform.
-__device__ __forceinline__ uint32_t fr_inv_exp_word(uint32_t w) {
-    uint32_t v = Fr::mod(0) - 2u;  // the low word is >= 2: no borrow
-#pragma unroll
-    for (uint32_t i = 1; i < 8; i++) v = w == i ? Fr::mod(i) : v;
-    return v;
-}
-__device__ __forceinline__ void fr_inv_fermat(fp256& o, const fp256& a) {
-    fp256 acc, base = a;
-    ff_set_one<Fr>(acc);
-#pragma unroll 1
-    for (uint32_t w = 0; w < 8; w++) {
-        const uint32_t bits = fr_inv_exp_word(w);
-#pragma unroll 1
-        for (uint32_t b = 0; b < 32; b++) {
-            if ((bits >> b) & 1) ff_mul<Fr>(acc, acc, base);
-            ff_sqr<Fr>(base, base);
-        }
-    }
-    o = acc;
 }
 
 // x[k] = src[k] for k < e and k < cnt, else one. src points at the thread's
@@ -173,13 +134,13 @@ __device__ __forceinline__ void tile_invert(uint4* lds4, uint32_t t,
     tree_up(lds4, t, inv);
     if (t < 64) {
         fp256 root, rinv;
-        tree_ld(lds4, 1, root);
-        fr_inv_fermat(rinv, root);
-        if (t == 0) tree_st(lds4, 1, rinv);
+        lds_split_ld(lds4, 1, POLY_H, root);
+        ff_inv<Fr>(rinv, root);
+        if (t == 0) lds_split_st(lds4, 1, POLY_H, rinv);
     }
     __syncthreads();
     tree_down<true>(lds4, t);
-    tree_ld(lds4, POLY_THREADS + t, inv);  // (thread total)^-1
+    lds_split_ld(lds4, POLY_THREADS + t, POLY_H, inv);  // (thread total)^-1
     // backward sweep: inv = (x[0] .. x[k])^-1 on entry to step k
 #pragma unroll
     for (uint32_t k = POLY_E_MAX - 1; k >= 1; k--) {
@@ -240,7 +201,7 @@ __global__ __launch_bounds__(POLY_THREADS) void k_gp_ratio(
         if (k < e) ff_mul<Fr>(tot, tot, u[k]);
     tree_up(lds4, t, tot);
     if (t == 0) {
-        tree_ld(lds4, 1, tot);
+        lds_split_ld(lds4, 1, POLY_H, tot);
         prods[blockIdx.x] = tot;
     }
 }
@@ -258,12 +219,13 @@ __device__ __forceinline__ void tile_scan(uint4* lds4, uint32_t t,
     load_own(x, src + first, own, e);
     own_prefixes(p, pre, x, e);
     tree_up(lds4, t, pre);
-    tree_ld(lds4, 1, total);
+    lds_split_ld(lds4, 1, POLY_H, total);
     __syncthreads();
-    if (t == 0) tree_st(lds4, 1, seed);
+    if (t == 0) lds_split_st(lds4, 1, POLY_H, seed);
     __syncthreads();
     tree_down<false>(lds4, t);
-    tree_ld(lds4, POLY_THREADS + t, pre);  // seed * everything before x[0]
+    // seed * everything before x[0]
+    lds_split_ld(lds4, POLY_THREADS + t, POLY_H, pre);
     if (own > 0) dst[first] = pre;
 #pragma unroll
     for (uint32_t k = 1; k < POLY_E_MAX; k++) {
