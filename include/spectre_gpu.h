@@ -1,4 +1,8 @@
 /* spectre_gpu.h — C ABI of the MI355X-native BN254 MSM/NTT proving backend.
+ * Besides the two transforms it carries the per-column stages that keep a
+ * proof's polynomials on the device between them: gate evaluation and vector
+ * ops (quotient phase), batch inverse and grand product (Z columns), and
+ * polynomial evaluation and (X - z) division (opening phase).
  *
  * This is the drop-in boundary for the Spectre/halo2 proving hot path: the
  * reference's own seam is the pair of free functions
@@ -260,6 +264,33 @@ int spectre_gpu_fr_grand_product(spectre_gpu_ctx*, int dev, const void* d_num,
  * default (tests, tuning). Result bytes do not depend on it. */
 int spectre_gpu_set_fr_scan_tile(spectre_gpu_ctx*, uint32_t elems);
 uint32_t spectre_gpu_fr_scan_tile_default(void); /* host-only, pure */
+
+/* ---- opening phase (device buffers, Montgomery Fr) -----------------------
+ * Between the last challenge and the two multiopen commits halo2 evaluates
+ * every queried coefficient-form polynomial at x*omega^rot
+ * (eval_polynomial) and divides by (X - z) per opening point
+ * (kate_division). These two calls do both on the buffers the inverse NTT
+ * left on device `dev`, so no polynomial is downloaded; the calls
+ * synchronize. Points, z and results are host memory. The workgroup tile is
+ * the one spectre_gpu_set_fr_scan_tile sets; result bytes do not depend on
+ * it. */
+#define SPECTRE_POLY_EVAL_MAX_POINTS 8u
+/* out[p] = sum_{i<n} a[i] * points[p]^i for p < npoints, one read of a.
+ * d_coeffs: device, n elements. points/out: host, npoints*32 B.
+ * n == 0: every out[p] = 0. 1 <= npoints <= MAX_POINTS. n <= 2^28. */
+int spectre_gpu_fr_poly_eval(spectre_gpu_ctx*, int dev, const void* d_coeffs,
+                             uint64_t n, const uint8_t* points,
+                             uint32_t npoints, uint8_t* out);
+/* a(X) = (X - z) * q(X) + rem:
+ *   q[i] = sum_{j=i+1}^{n-1} a[j] * z^(j-i-1)  for i < n   (so q[n-1] = 0)
+ *   rem  = a(z)
+ * q[0 .. n-1) is exactly halo2's kate_division(a, z). d_q has n elements
+ * and may alias d_a. out_rem may be NULL. n == 0: rem = 0, nothing is
+ * written. No inverse of z is taken: z = 0 and z = 1 are ordinary inputs.
+ * n <= 2^28. */
+int spectre_gpu_fr_poly_div_linear(spectre_gpu_ctx*, int dev, const void* d_a,
+                                   const uint8_t z[32], void* d_q, uint64_t n,
+                                   uint8_t out_rem[32]);
 
 /* ---- device memory helpers (for C callers and the bench harness) ------- */
 int spectre_gpu_malloc(spectre_gpu_ctx*, int dev, size_t bytes, void** d_ptr);

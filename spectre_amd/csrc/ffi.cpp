@@ -600,6 +600,50 @@ uint32_t spectre_gpu_fr_scan_tile_default(void) {
     return fr_scan_tile_default();
 }
 
+// ---------------------------------------------------------------- opening phase
+int spectre_gpu_fr_poly_eval(spectre_gpu_ctx* ctx, int dev,
+                             const void* d_coeffs, uint64_t n,
+                             const uint8_t* points, uint32_t npoints,
+                             uint8_t* out) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_coeffs || !points || !out) {
+        set_err("fr_poly_eval: null %s",
+                d_coeffs ? "points/out" : "device pointer");
+        return -1;
+    }
+    if (npoints < 1 || npoints > SPECTRE_POLY_EVAL_MAX_POINTS) {
+        set_err("fr_poly_eval: npoints %u outside [1, %u]", npoints,
+                SPECTRE_POLY_EVAL_MAX_POINTS);
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 pts[SPECTRE_POLY_EVAL_MAX_POINTS], vals[SPECTRE_POLY_EVAL_MAX_POINTS];
+    for (uint32_t p = 0; p < npoints; p++) ff_from_bytes(pts[p], points + 32 * p);
+    RC_TRY(fr_poly_eval_device(ctx, dev, (const fp256*)d_coeffs, n, pts,
+                               npoints, vals));
+    for (uint32_t p = 0; p < npoints; p++) ff_to_bytes(out + 32 * p, vals[p]);
+    return 0;
+}
+
+int spectre_gpu_fr_poly_div_linear(spectre_gpu_ctx* ctx, int dev,
+                                   const void* d_a, const uint8_t z[32],
+                                   void* d_q, uint64_t n,
+                                   uint8_t out_rem[32]) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_a || !d_q || !z) {
+        set_err("fr_poly_div_linear: null %s",
+                z ? "device pointer" : "z");
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 zv, rem;
+    ff_from_bytes(zv, z);
+    RC_TRY(fr_poly_div_linear_device(ctx, dev, (const fp256*)d_a, zv,
+                                     (fp256*)d_q, n, out_rem ? &rem : nullptr));
+    if (out_rem) ff_to_bytes(out_rem, rem);
+    return 0;
+}
+
 // ---------------------------------------------------------------- memory
 int spectre_gpu_malloc(spectre_gpu_ctx* ctx, int dev, size_t bytes,
                        void** d_ptr) {

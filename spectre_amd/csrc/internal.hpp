@@ -169,12 +169,18 @@ struct DeviceState {
     // total in the last slot), and the pinned landing spot of that total ----
     DevBuf<fp256> d_gp_prods;
     PinnedBuf<fp256> h_gp_last;
+    // ---- opening-phase scratch: every level of tile partials of one
+    // evaluation / division (per point), and the pinned landing spot of the
+    // evaluations / the remainder ----
+    DevBuf<fp256> d_poly_parts;
+    PinnedBuf<fp256> h_poly_out;
     std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n
     // frees everything this device owns; the caller has made it current
     void release() {
         for (auto& sl : slots) sl.release(stream);
         release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
-                    d_ntt_io, d_cosetA, d_gate, d_gp_prods, h_gp_last);
+                    d_ntt_io, d_cosetA, d_gate, d_gp_prods, h_gp_last,
+                    d_poly_parts, h_poly_out);
         for (auto& kv : bases_cache) kv.second.release();
         bases_cache.clear();
         for (auto& kv : plans) kv.second.release();
@@ -262,7 +268,17 @@ int fr_batch_invert_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
 int fr_grand_product_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_num,
                             const fp256* d_den, const fp256& z0, fp256* d_z,
                             uint64_t n, fp256* out_last);
-// poly.hip — the built-in tile of the two calls above, and whether a
+// poly.hip — out[p] = sum_i coeffs[i] * points[p]^i for 1..8 host points,
+// one read of d_coeffs (synchronizes). points / out are host memory.
+int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
+                        uint64_t n, const fp256* points, uint32_t npoints,
+                        fp256* out);
+// poly.hip — a(X) = (X - z) q(X) + rem: q -> d_q (n elements, q[n-1] = 0),
+// *out_rem (may be null) = a(z) (synchronizes). d_q may alias d_a.
+int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
+                              const fp256& z, fp256* d_q, uint64_t n,
+                              fp256* out_rem);
+// poly.hip — the built-in tile of the calls above, and whether a
 // ctx->fr_scan_tile value is usable (pure; host).
 uint32_t fr_scan_tile_default();
 bool fr_scan_tile_valid(uint32_t elems);

@@ -1,4 +1,5 @@
-// poly.hip — Fr batch inversion and grand (running) products for gfx950.
+// poly.hip — Fr batch inversion and grand (running) products, and the opening
+// phase's polynomial evaluation and (X - z) division, for gfx950.
 //
 // What halo2's permutation and lookup arguments do per Z column:
 //   batch_invert(den); r = num * den^-1; Z[0] = z0, Z[i+1] = Z[i] * r[i]
@@ -31,7 +32,40 @@
 // There is no inter-workgroup waiting inside any kernel. Every thread reads
 // all of its inputs before it writes its outputs and touches only its own
 // indices, which is what lets d_out / d_z alias an input.
+//
+// Opening phase: eval_polynomial and kate_division on the same tiles, with
+// zero for padding and a second, ADDITIVE tree with weights. For a point x a
+// thread forms S = sum_k a[f+k] x^k over its e coefficients by Horner from
+// the top, and the up-sweep combines
+//   node = left + x^(len_left) * right               -> root = tile partial
+// with the eight weights x^(e*2^l) taken from a host-built table in the
+// kernel arguments. The tile partials P_b = sum_k a[bT+k] x^k are a
+// polynomial P with a(x) = P(x^T), so
+//   evaluation  is k_poly_tile_eval run to a fixed point: the host loops
+//               n -> ceil(n/T) -> .. -> 1, raising the point to the T-th
+//               power per level; there is no separate final reduction. For
+//               several points a thread keeps its coefficients in registers
+//               and loops the points (one read of a); above the first level
+//               each point has its own vector, on gridDim.y.
+//   division    a(X) = (X - z) q(X) + rem is reduce-then-scan over the same
+//               partials from the top index down. With Q[i] the quotient at
+//               index i, the seed of tile b is Q[(b+1)T - 1] = C_b where
+//               C = div(P, z^T): the same problem one level up. The host
+//               evaluates partials level by level until one tile remains,
+//               divides that tile with seed 0 (its root is rem = a(z)), and
+//               descends with one k_poly_div_scan per level, each tile seeded
+//               from the level above; partial vectors become their quotients
+//               in place. In a tile the down-sweep hands a node's seed to its
+//               right child and S_right + z^(len_right) * seed to its left
+//               child; thread t then has q[f+e-1] = seed_t and
+//               q[k] = a[k+1] + z q[k+1] down to k = f.
+// No inverse of z is taken, so z = 0 and z = 1 are ordinary inputs. Field
+// addition and multiplication are exact, so here too the result bytes depend
+// neither on the tile size nor on the association order. A thread reads all
+// of a[f, f+e) before it writes q[f, f+e) and touches no other index of
+// either, which is what lets d_q alias d_a.
 #include "internal.hpp"
+#include "poly_levels.hpp"
 
 #define POLY_THREADS 256
 #define POLY_E_MAX 4  // elements per thread at the default tile
@@ -266,6 +300,159 @@ __global__ __launch_bounds__(POLY_THREADS) void k_gp_scan(
               (int64_t)(n - base), seed, e, total);
 }
 
+// ------------------------------------------------------------ opening phase
+#define POLY_TREE_LEVELS 8  // log2(POLY_THREADS)
+static_assert(1u << POLY_TREE_LEVELS == POLY_THREADS, "one weight per level");
+// Powers of one point for a launch with e elements per thread, built on the
+// host: w[0] = x, w[1 + l] = x^(e * 2^l), the weight of a right child whose
+// left sibling spans 2^l threads.
+struct PolyPow {
+    fp256 w[1 + POLY_TREE_LEVELS];
+};
+struct PolyPows {
+    PolyPow pt[SPECTRE_POLY_EVAL_MAX_POINTS];
+};
+
+// x[k] = src[k] for k < e and k < cnt, else zero (load_own with the additive
+// identity).
+__device__ __forceinline__ void load_own_zero(fp256 (&x)[POLY_E_MAX],
+                                              const fp256* src, int64_t cnt,
+                                              uint32_t e) {
+#pragma unroll
+    for (uint32_t k = 0; k < POLY_E_MAX; k++) {
+        if (k < e && (int64_t)k < cnt) x[k] = src[k];
+        else ff_set_zero(x[k]);
+    }
+}
+
+// s = sum_{k<e} a[k] x^k by Horner from the top (a[k] = 0 for k >= e).
+__device__ __forceinline__ void own_horner(fp256& s,
+                                           const fp256 (&a)[POLY_E_MAX],
+                                           const fp256& x, uint32_t e) {
+    s = a[POLY_E_MAX - 1];
+#pragma unroll
+    for (int k = POLY_E_MAX - 2; k >= 0; k--) {
+        if ((uint32_t)k + 1 < e) ff_mul<Fr>(s, s, x);
+        ff_add<Fr>(s, s, a[k]);
+    }
+}
+
+// leaves <- v, then the weighted additive up-sweep: node = left + w * right,
+// w = pw.w[1 + l] at the level whose children span 2^l threads. On return
+// every node holds the Horner value of its subtree, node 1 the tile's. Same
+// barriers as tree_up.
+__device__ __forceinline__ void wtree_up(uint4* lds4, uint32_t t,
+                                         const fp256& v, const PolyPow& pw) {
+    __syncthreads();
+    lds_split_st(lds4, POLY_THREADS + t, POLY_H, v);
+    __syncthreads();
+    uint32_t l = 0;
+    for (uint32_t w = POLY_THREADS / 2; w >= 1; w >>= 1, l++) {
+        if (t < w) {
+            fp256 a, b, c;
+            lds_split_ld(lds4, 2 * (w + t), POLY_H, a);
+            lds_split_ld(lds4, 2 * (w + t) + 1, POLY_H, b);
+            ff_mul<Fr>(c, b, pw.w[1 + l]);
+            ff_add<Fr>(c, c, a);
+            lds_split_st(lds4, w + t, POLY_H, c);
+        }
+        __syncthreads();
+    }
+}
+
+// Down-sweep of the division after wtree_up, node 1 holding the tile's seed
+// (the quotient value just above the tile): a node's seed goes to its right
+// child, and S_right + w * seed to its left child, w = z^(len_right). Leaf
+// POLY_THREADS + t ends up holding the quotient value just above thread t's
+// elements.
+__device__ __forceinline__ void wtree_down(uint4* lds4, uint32_t t,
+                                           const PolyPow& pw) {
+    uint32_t l = POLY_TREE_LEVELS;
+    for (uint32_t w = 1; w <= POLY_THREADS / 2; w <<= 1) {
+        l--;
+        if (t < w) {
+            const uint32_t i = w + t;
+            fp256 x, r, o;
+            lds_split_ld(lds4, i, POLY_H, x);
+            lds_split_ld(lds4, 2 * i + 1, POLY_H, r);
+            ff_mul<Fr>(o, x, pw.w[1 + l]);
+            ff_add<Fr>(o, o, r);
+            lds_split_st(lds4, 2 * i, POLY_H, o);
+            lds_split_st(lds4, 2 * i + 1, POLY_H, x);
+        }
+        __syncthreads();
+    }
+}
+
+// Tile partials. Block (b, y) reads tile b of the n-element vector
+// src + y * src_stride once and, for each of its ppb points
+// p = y * ppb + j, writes sum_k src[bT + k] x_p^k to
+// partials[p * part_stride + b]. The first level runs one y with all the
+// points (one read of the coefficients), the levels above one point per y.
+__global__ __launch_bounds__(POLY_THREADS) void k_poly_tile_eval(
+    const fp256* __restrict__ src, uint64_t src_stride, uint64_t n,
+    fp256* __restrict__ partials, uint64_t part_stride, uint32_t ppb,
+    uint32_t e, const PolyPows pws) {
+    __shared__ uint4 lds4[2 * POLY_H];
+    const uint32_t t = threadIdx.x;
+    const uint64_t first = ((uint64_t)blockIdx.x * POLY_THREADS + t) * e;
+    const int64_t cnt = (int64_t)n - (int64_t)first;
+    fp256 a[POLY_E_MAX];
+    load_own_zero(a, src + blockIdx.y * src_stride + first, cnt, e);
+    for (uint32_t j = 0; j < ppb; j++) {
+        const uint32_t p = blockIdx.y * ppb + j;
+        const PolyPow& pw = pws.pt[p];
+        fp256 s;
+        own_horner(s, a, pw.w[0], e);
+        wtree_up(lds4, t, s, pw);
+        if (t == 0) {
+            lds_split_ld(lds4, 1, POLY_H, s);
+            partials[p * part_stride + blockIdx.x] = s;
+        }
+    }
+}
+
+// One level of the division: dst[i] = the quotient of the n-element vector
+// src by (X - z) at index i, given seeds[b] = the quotient value just above
+// tile b (null: zero, the top level). src and dst may be the same. rem_out
+// (null below the top level, where there is one tile) receives the tile's
+// Horner value, which at the top is a(z).
+__global__ __launch_bounds__(POLY_THREADS) void k_poly_div_scan(
+    const fp256* src, fp256* dst, const fp256* __restrict__ seeds, uint64_t n,
+    fp256* __restrict__ rem_out, uint32_t e, const PolyPow pw) {
+    __shared__ uint4 lds4[2 * POLY_H];
+    const uint32_t t = threadIdx.x;
+    const uint64_t first = ((uint64_t)blockIdx.x * POLY_THREADS + t) * e;
+    const int64_t cnt = (int64_t)n - (int64_t)first;
+    fp256 a[POLY_E_MAX], q;
+    load_own_zero(a, src + first, cnt, e);
+    own_horner(q, a, pw.w[0], e);
+    wtree_up(lds4, t, q, pw);
+    if (t == 0) {
+        if (rem_out) {
+            lds_split_ld(lds4, 1, POLY_H, q);
+            *rem_out = q;
+        }
+        if (seeds) q = seeds[blockIdx.x];
+        else ff_set_zero(q);
+        lds_split_st(lds4, 1, POLY_H, q);
+    }
+    __syncthreads();
+    wtree_down(lds4, t, pw);
+    lds_split_ld(lds4, POLY_THREADS + t, POLY_H, q);  // q[first + e - 1]
+    // the guards are wave-uniform in k and e; a[k] beyond e or n is zero
+#pragma unroll
+    for (int k = POLY_E_MAX - 1; k >= 0; k--) {
+        if ((uint32_t)k < e) {
+            if ((int64_t)k < cnt) dst[first + k] = q;
+            if (k > 0) {
+                ff_mul<Fr>(q, q, pw.w[0]);
+                ff_add<Fr>(q, q, a[k]);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- host side
 uint32_t fr_scan_tile_default() { return POLY_TILE_DEFAULT; }
 
@@ -334,5 +521,133 @@ int fr_grand_product_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_num,
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
     if (out_last) *out_last = *ds.h_gp_last.ptr;
+    return 0;
+}
+
+// The table of x for a launch with e elements per thread; returns x^(256 e),
+// the point of the level above.
+static fp256 poly_pow_table(PolyPow& pw, const fp256& x, uint32_t e) {
+    pw.w[0] = x;
+    ff_pow_u32<Fr>(pw.w[1], x, e);
+    for (int l = 1; l < POLY_TREE_LEVELS; l++)
+        ff_sqr<Fr>(pw.w[1 + l], pw.w[l]);
+    fp256 up;
+    ff_sqr<Fr>(up, pw.w[POLY_TREE_LEVELS]);
+    return up;
+}
+
+static uint32_t poly_tiles(uint64_t n, uint64_t tile) {
+    return (uint32_t)((n + tile - 1) / tile);
+}
+
+int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
+                        uint64_t n, const fp256* points, uint32_t npoints,
+                        fp256* out) {
+    if (n > POLY_MAX_N) {
+        set_err("fr_poly_eval: n %llu > 2^28", (unsigned long long)n);
+        return -1;
+    }
+    if (n == 0) {
+        for (uint32_t p = 0; p < npoints; p++) ff_set_zero(out[p]);
+        return 0;
+    }
+    DeviceState& ds = ctx->devs[dev];
+    HIP_TRY(hipSetDevice(ds.device_id));
+    const uint32_t e = elems_per_thread(ctx);
+    const uint64_t tile = (uint64_t)POLY_THREADS * e;
+    // partial vectors down to one element per point; level l holds npoints
+    // vectors of size[l] from element npoints * off[l]
+    const PolyLevels lv = poly_levels(n, tile, 1, 1);
+    if (!lv.ok) {
+        set_err("fr_poly_eval: level table overflow at n %llu",
+                (unsigned long long)n);
+        return -1;
+    }
+    RC_TRY(ds.d_poly_parts.reserve((size_t)(npoints * lv.total)));
+    RC_TRY(ds.h_poly_out.reserve(SPECTRE_POLY_EVAL_MAX_POINTS));
+    fp256 x[SPECTRE_POLY_EVAL_MAX_POINTS];
+    for (uint32_t p = 0; p < npoints; p++) x[p] = points[p];
+    const fp256* src = d_coeffs;
+    uint64_t m = n;
+    for (uint32_t l = 0; l < lv.count; l++) {
+        PolyPows pws{};
+        for (uint32_t p = 0; p < npoints; p++)
+            x[p] = poly_pow_table(pws.pt[p], x[p], e);
+        fp256* dst = ds.d_poly_parts.ptr + npoints * lv.off[l];
+        // the coefficients serve every point; above them, a vector per point
+        const uint32_t ny = l == 0 ? 1 : npoints;
+        hipLaunchKernelGGL(k_poly_tile_eval, dim3(poly_tiles(m, tile), ny),
+                           dim3(POLY_THREADS), 0, ds.stream, src, m, m, dst,
+                           lv.size[l], npoints / ny, e, pws);
+        src = dst;
+        m = lv.size[l];
+    }
+    // the last level is one element per point, contiguous
+    HIP_TRY(hipMemcpyAsync(ds.h_poly_out.ptr, src, npoints * sizeof(fp256),
+                           hipMemcpyDeviceToHost, ds.stream));
+    HIP_TRY(hipStreamSynchronize(ds.stream));
+    HIP_TRY(hipGetLastError());
+    for (uint32_t p = 0; p < npoints; p++) out[p] = ds.h_poly_out.ptr[p];
+    return 0;
+}
+
+int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
+                              const fp256& z, fp256* d_q, uint64_t n,
+                              fp256* out_rem) {
+    if (n > POLY_MAX_N) {
+        set_err("fr_poly_div_linear: n %llu > 2^28", (unsigned long long)n);
+        return -1;
+    }
+    if (n == 0) {
+        if (out_rem) ff_set_zero(*out_rem);
+        return 0;
+    }
+    DeviceState& ds = ctx->devs[dev];
+    HIP_TRY(hipSetDevice(ds.device_id));
+    const uint32_t e = elems_per_thread(ctx);
+    const uint64_t tile = (uint64_t)POLY_THREADS * e;
+    // partial vectors until one fits a tile; one more element for a(z)
+    const PolyLevels lv = poly_levels(n, tile, tile, 0);
+    if (!lv.ok) {
+        set_err("fr_poly_div_linear: level table overflow at n %llu",
+                (unsigned long long)n);
+        return -1;
+    }
+    RC_TRY(ds.d_poly_parts.reserve((size_t)lv.total + 1));
+    RC_TRY(ds.h_poly_out.reserve(SPECTRE_POLY_EVAL_MAX_POINTS));
+    fp256* parts = ds.d_poly_parts.ptr;
+    fp256* d_rem = parts + lv.total;
+    // vec[0] = a, vec[l] = the partials of vec[l - 1], at the point zl[l]
+    const fp256* vec[POLY_MAX_LEVELS + 1];
+    uint64_t len[POLY_MAX_LEVELS + 1];
+    PolyPow zl[POLY_MAX_LEVELS + 1];
+    vec[0] = d_a;
+    len[0] = n;
+    fp256 x = z;
+    for (uint32_t l = 0; l <= lv.count; l++) {
+        x = poly_pow_table(zl[l], x, e);
+        if (l == lv.count) break;
+        vec[l + 1] = parts + lv.off[l];
+        len[l + 1] = lv.size[l];
+        PolyPows one{};
+        one.pt[0] = zl[l];
+        hipLaunchKernelGGL(k_poly_tile_eval, dim3(poly_tiles(len[l], tile), 1),
+                           dim3(POLY_THREADS), 0, ds.stream, vec[l], len[l],
+                           len[l], parts + lv.off[l], lv.size[l], 1u, e, one);
+    }
+    for (int l = (int)lv.count; l >= 0; l--) {
+        const bool top = l == (int)lv.count;
+        hipLaunchKernelGGL(k_poly_div_scan, dim3(poly_tiles(len[l], tile)),
+                           dim3(POLY_THREADS), 0, ds.stream, vec[l],
+                           l == 0 ? d_q : parts + lv.off[l - 1],
+                           top ? (const fp256*)nullptr : vec[l + 1], len[l],
+                           top ? d_rem : (fp256*)nullptr, e, zl[l]);
+    }
+    if (out_rem)
+        HIP_TRY(hipMemcpyAsync(ds.h_poly_out.ptr, d_rem, sizeof(fp256),
+                               hipMemcpyDeviceToHost, ds.stream));
+    HIP_TRY(hipStreamSynchronize(ds.stream));
+    HIP_TRY(hipGetLastError());
+    if (out_rem) *out_rem = *ds.h_poly_out.ptr;
     return 0;
 }

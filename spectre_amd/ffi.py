@@ -150,6 +150,16 @@ def load_library() -> ctypes.CDLL:
     lib.spectre_gpu_set_fr_scan_tile.argtypes = [c.c_void_p, c.c_uint32]
     lib.spectre_gpu_fr_scan_tile_default.restype = c.c_uint32
     lib.spectre_gpu_fr_scan_tile_default.argtypes = []
+    lib.spectre_gpu_fr_poly_eval.restype = c.c_int
+    lib.spectre_gpu_fr_poly_eval.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint32,
+        c.c_void_p,
+    ]
+    lib.spectre_gpu_fr_poly_div_linear.restype = c.c_int
+    lib.spectre_gpu_fr_poly_div_linear.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
+        c.c_void_p,
+    ]
     lib.spectre_gpu_malloc.restype = c.c_int
     lib.spectre_gpu_malloc.argtypes = [c.c_void_p, c.c_int, c.c_size_t,
                                        c.POINTER(c.c_void_p)]
@@ -479,6 +489,37 @@ class SpectreGpu:
         default. Results do not change."""
         rc = self._lib.spectre_gpu_set_fr_scan_tile(self._ctx, elems)
         self._check(rc, "set_fr_scan_tile")
+
+    POLY_EVAL_MAX_POINTS = 8  # = SPECTRE_POLY_EVAL_MAX_POINTS
+
+    def fr_poly_eval(self, d_coeffs: int, n: int, points: list[bytes],
+                     dev: int = 0) -> list[bytes]:
+        """[sum_i d_coeffs[i] * x^i for x in points] over n Montgomery Fr
+        coefficients on the device, read once for all of the 1..8 points."""
+        assert all(len(p) == 32 for p in points)
+        npts = len(points)
+        raw = b"".join(points)
+        pts = (ctypes.c_uint8 * max(32, len(raw))).from_buffer_copy(
+            raw.ljust(32, b"\0"))
+        out = (ctypes.c_uint8 * max(32, 32 * npts))()
+        rc = self._lib.spectre_gpu_fr_poly_eval(
+            self._ctx, dev, ctypes.c_void_p(d_coeffs), n, pts, npts, out)
+        self._check(rc, "fr_poly_eval")
+        raw = bytes(out)
+        return [raw[32 * i:32 * (i + 1)] for i in range(npts)]
+
+    def fr_poly_div_linear(self, d_a: int, z: bytes, d_q: int, n: int,
+                           dev: int = 0) -> bytes:
+        """d_q[i] = sum_{j>i} d_a[j] * z^(j-i-1) for i < n, the quotient of
+        a(X) by (X - z) (d_q[:n-1] is halo2's kate_division, d_q[n-1] = 0).
+        Returns the remainder a(z). d_q may equal d_a."""
+        zz = (ctypes.c_uint8 * 32).from_buffer_copy(z)
+        rem = (ctypes.c_uint8 * 32)()
+        rc = self._lib.spectre_gpu_fr_poly_div_linear(
+            self._ctx, dev, ctypes.c_void_p(d_a), zz, ctypes.c_void_p(d_q), n,
+            rem)
+        self._check(rc, "fr_poly_div_linear")
+        return bytes(rem)
 
     # ---- device memory helpers ----
     def malloc(self, nbytes: int, dev: int = 0) -> int:
