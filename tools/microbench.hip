@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256, 2) void k_mul2_chain(const g1_affine* pts,
 
 // correctness: ff_mul_cols must equal ff_mul bit-for-bit on pseudorandom
 // reduced inputs (both Fq and Fr), chained so errors compound and surface.
+// The suite's check of the same is tests/test_field_probe.py (edge operands, against bigints).
 __global__ void k_mul_cols_check(uint32_t* bad, int nwork) {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nwork) return;
