@@ -1,8 +1,9 @@
 /* spectre_gpu.h — C ABI of the MI355X-native BN254 MSM/NTT proving backend.
  * Besides the two transforms it carries the per-column stages that keep a
  * proof's polynomials on the device between them: gate evaluation and vector
- * ops (quotient phase), batch inverse and grand product (Z columns), and
- * polynomial evaluation and (X - z) division (opening phase).
+ * ops (quotient phase), batch inverse and grand product (Z columns), the
+ * lookup argument's sorted input and permuted table columns, and polynomial
+ * evaluation and (X - z) division (opening phase).
  *
  * This is the drop-in boundary for the Spectre/halo2 proving hot path: the
  * reference's own seam is the pair of free functions
@@ -291,6 +292,27 @@ int spectre_gpu_fr_poly_eval(spectre_gpu_ctx*, int dev, const void* d_coeffs,
 int spectre_gpu_fr_poly_div_linear(spectre_gpu_ctx*, int dev, const void* d_a,
                                    const uint8_t z[32], void* d_q, uint64_t n,
                                    uint8_t out_rem[32]);
+
+/* ---- lookup argument (device buffers, Montgomery Fr) ---------------------
+ * halo2's permute_expression_pair over the u usable rows of a lookup's
+ * compressed input column A and table column S (u = n - blinding_factors -
+ * 1; the caller fills the blinding rows afterwards, as it does today).
+ * A' = A[0..u) sorted by canonical value; S' as halo2's
+ * permute_expression_pair builds it. Montgomery Fr, device buffers on `dev`;
+ * exactly u elements of each output are written. The four buffers must not
+ * overlap. u == 0: nothing is written. u <= 2^28. Synchronizes.
+ * Every row then has A'[i] == S'[i] or A'[i] == A'[i-1]. The order is
+ * Fr::cmp's, of the integer a and not of its Montgomery image; elements are
+ * reduced residues. An input value that the table does not hold fails the
+ * call with SPECTRE_ERR_LOOKUP_MISS (halo2: Error::ConstraintSystemFailure);
+ * spectre_gpu_last_error() then gives the number of distinct input values
+ * that were missing, and the output contents are unspecified. The inputs
+ * are never written. */
+#define SPECTRE_ERR_LOOKUP_MISS (-5)
+int spectre_gpu_fr_lookup_permute(spectre_gpu_ctx*, int dev,
+                                  const void* d_input, const void* d_table,
+                                  void* d_input_perm, void* d_table_perm,
+                                  uint64_t u);
 
 /* ---- device memory helpers (for C callers and the bench harness) ------- */
 int spectre_gpu_malloc(spectre_gpu_ctx*, int dev, size_t bytes, void** d_ptr);

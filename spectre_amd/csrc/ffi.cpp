@@ -644,6 +644,42 @@ int spectre_gpu_fr_poly_div_linear(spectre_gpu_ctx* ctx, int dev,
     return 0;
 }
 
+// ---------------------------------------------------------------- lookup argument
+int spectre_gpu_fr_lookup_permute(spectre_gpu_ctx* ctx, int dev,
+                                  const void* d_input, const void* d_table,
+                                  void* d_input_perm, void* d_table_perm,
+                                  uint64_t u) {
+    if (check_dev(ctx, dev)) return -1;
+    const void* buf[4] = {d_input, d_table, d_input_perm, d_table_perm};
+    static const char* const name[4] = {"d_input", "d_table", "d_input_perm",
+                                        "d_table_perm"};
+    for (int i = 0; i < 4; i++) {
+        if (!buf[i]) {
+            set_err("fr_lookup_permute: null device pointer %s", name[i]);
+            return -1;
+        }
+    }
+    if (u > (1ull << 28)) {
+        set_err("fr_lookup_permute: u %llu > 2^28", (unsigned long long)u);
+        return -1;
+    }
+    for (int i = 0; i < 4; i++) {
+        for (int j = i + 1; j < 4; j++) {
+            const uintptr_t a = (uintptr_t)buf[i], b = (uintptr_t)buf[j];
+            if (a < b + 32 * u && b < a + 32 * u) {
+                set_err("fr_lookup_permute: %s and %s overlap", name[i],
+                        name[j]);
+                return -1;
+            }
+        }
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    return fr_lookup_permute_device(ctx, dev, (const fp256*)d_input,
+                                    (const fp256*)d_table,
+                                    (fp256*)d_input_perm,
+                                    (fp256*)d_table_perm, u);
+}
+
 // ---------------------------------------------------------------- memory
 int spectre_gpu_malloc(spectre_gpu_ctx* ctx, int dev, size_t bytes,
                        void** d_ptr) {

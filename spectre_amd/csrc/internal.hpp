@@ -174,13 +174,24 @@ struct DeviceState {
     // evaluations / the remainder ----
     DevBuf<fp256> d_poly_parts;
     PinnedBuf<fp256> h_poly_out;
+    // ---- lookup-permutation scratch (lookup.hip), u rows per call ----
+    DevBuf<fp256> d_lk_canon;    // 2u: canonical input | canonical table;
+                                 // the first half then takes canonical Ss
+    DevBuf<fp256> d_lk_ss;       // u: the sorted table, Montgomery
+    DevBuf<uint64_t> d_lk_keys;  // 2u: one limb's sort keys, in | out
+    DevBuf<uint32_t> d_lk_idx;   // 7u: two permutations, the flags !first
+                                 // and free, their ranks, repeated rows
+    DevBuf<uint8_t> d_lk_tmp;    // hipCUB sort / scan temp storage (bytes)
+    DevBuf<uint32_t> d_lk_words; // OR of the canonical limbs, miss count
+    PinnedBuf<uint32_t> h_lk_words;  // their pinned landing spot
     std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n
     // frees everything this device owns; the caller has made it current
     void release() {
         for (auto& sl : slots) sl.release(stream);
         release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
                     d_ntt_io, d_cosetA, d_gate, d_gp_prods, h_gp_last,
-                    d_poly_parts, h_poly_out);
+                    d_poly_parts, h_poly_out, d_lk_canon, d_lk_ss, d_lk_keys,
+                    d_lk_idx, d_lk_tmp, d_lk_words, h_lk_words);
         for (auto& kv : bases_cache) kv.second.release();
         bases_cache.clear();
         for (auto& kv : plans) kv.second.release();
@@ -282,3 +293,12 @@ int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
 // ctx->fr_scan_tile value is usable (pure; host).
 uint32_t fr_scan_tile_default();
 bool fr_scan_tile_valid(uint32_t elems);
+
+// lookup.hip — halo2's permute_expression_pair over u <= 2^28 rows: the
+// input sorted by canonical value -> d_input_perm, the matching table
+// arrangement -> d_table_perm (synchronizes). SPECTRE_ERR_LOOKUP_MISS when
+// an input value is not in the table. The four buffers do not overlap.
+int fr_lookup_permute_device(spectre_gpu_ctx* ctx, int dev,
+                             const fp256* d_input, const fp256* d_table,
+                             fp256* d_input_perm, fp256* d_table_perm,
+                             uint64_t u);

@@ -160,6 +160,11 @@ def load_library() -> ctypes.CDLL:
         c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
         c.c_void_p,
     ]
+    lib.spectre_gpu_fr_lookup_permute.restype = c.c_int
+    lib.spectre_gpu_fr_lookup_permute.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_uint64,
+    ]
     lib.spectre_gpu_malloc.restype = c.c_int
     lib.spectre_gpu_malloc.argtypes = [c.c_void_p, c.c_int, c.c_size_t,
                                        c.POINTER(c.c_void_p)]
@@ -520,6 +525,20 @@ class SpectreGpu:
             rem)
         self._check(rc, "fr_poly_div_linear")
         return bytes(rem)
+
+    ERR_LOOKUP_MISS = -5  # = SPECTRE_ERR_LOOKUP_MISS
+
+    def fr_lookup_permute(self, d_input: int, d_table: int, d_input_perm: int,
+                          d_table_perm: int, u: int, dev: int = 0) -> None:
+        """halo2's permute_expression_pair over u rows of Montgomery Fr on
+        the device: d_input_perm = d_input sorted by canonical value,
+        d_table_perm = d_table rearranged so that every row equals its input
+        row or the input row repeats the one above. The four buffers must not
+        overlap. An input value absent from the table raises with rc=-5."""
+        rc = self._lib.spectre_gpu_fr_lookup_permute(
+            self._ctx, dev, ctypes.c_void_p(d_input), ctypes.c_void_p(d_table),
+            ctypes.c_void_p(d_input_perm), ctypes.c_void_p(d_table_perm), u)
+        self._check(rc, "fr_lookup_permute")
 
     # ---- device memory helpers ----
     def malloc(self, nbytes: int, dev: int = 0) -> int:
