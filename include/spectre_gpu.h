@@ -192,6 +192,21 @@ int spectre_gpu_ntt_fr(spectre_gpu_ctx*, uint8_t* data, uint32_t log_n,
 int spectre_gpu_ntt_fr_device(spectre_gpu_ctx*, int dev, void* d_data,
                               uint32_t log_n, const uint8_t omega[32],
                               int inverse, const uint8_t* coset_gen);
+/* out[t] = sum_{i < n} a[i] * coset_gen^i * omega_ext^(i*t),  t < N,
+ * n = 2^log_n, N = 2^(log_n + ext_bits): halo2's coeff_to_extended
+ * (distribute_powers_zeta, resize with zeros, best_fft at extended_k).
+ * d_coeffs: n elements, d_out: N elements, device `dev`, Montgomery Fr.
+ * coset_gen NULL: no coset factor. ext_bits = 0 is the plain forward
+ * (coset) NTT out of place. log_n + ext_bits <= 28.
+ * d_out == d_coeffs is allowed (a buffer of N elements whose first n hold
+ * the coefficients); its other N - n elements are NEVER READ and need not be
+ * initialised. Otherwise the two ranges must not overlap, and d_coeffs is
+ * not written. Synchronizes. */
+int spectre_gpu_ntt_fr_extend_device(spectre_gpu_ctx*, int dev,
+                                     const void* d_coeffs, uint32_t log_n,
+                                     uint32_t ext_bits, void* d_out,
+                                     const uint8_t omega_ext[32],
+                                     const uint8_t* coset_gen);
 
 /* ---- pointwise Fr vector ops (device buffers, Montgomery form) ----------
  * The quotient phase evaluates gate expressions pointwise between the
@@ -241,6 +256,14 @@ int spectre_gpu_fr_vec_op(spectre_gpu_ctx*, int dev, int op,
                           const void* d_a, const void* d_b /* NULL for op 3 */,
                           const uint8_t c[32] /* NULL for ops 0-2 */,
                           void* d_out, uint64_t n);
+/* out[i] = a[i] * table[i mod period] — halo2's divide_by_vanishing_poly
+ * with table = t_evaluations. table: host, period*32 B, Montgomery Fr;
+ * period a power of two, 1 <= period <= SPECTRE_VEC_PERIOD_MAX (64).
+ * d_out may alias d_a. n == 0: nothing is done. Synchronizes. */
+#define SPECTRE_VEC_PERIOD_MAX 64u
+int spectre_gpu_fr_vec_mul_periodic(spectre_gpu_ctx*, int dev, const void* d_a,
+                                    const uint8_t* table, uint32_t period,
+                                    void* d_out, uint64_t n);
 
 /* ---- grand products (device buffers, Montgomery Fr) ---------------------
  * The permutation and lookup arguments build, per column,

@@ -494,6 +494,37 @@ int spectre_gpu_ntt_fr_device(spectre_gpu_ctx* ctx, int dev, void* d_data,
                       coset_gen ? &g : nullptr);
 }
 
+int spectre_gpu_ntt_fr_extend_device(spectre_gpu_ctx* ctx, int dev,
+                                     const void* d_coeffs, uint32_t log_n,
+                                     uint32_t ext_bits, void* d_out,
+                                     const uint8_t omega_ext[32],
+                                     const uint8_t* coset_gen) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_coeffs || !d_out || !omega_ext) {
+        set_err("ntt_extend: null %s",
+                omega_ext ? "device pointer" : "omega_ext");
+        return -1;
+    }
+    if (log_n > 28 || ext_bits > 28 - log_n) {
+        set_err("ntt_extend: log_n %u + ext_bits %u > 28 unsupported (Fr "
+                "2-adicity)", log_n, ext_bits);
+        return -3;
+    }
+    // d_out is d_coeffs or lies clear of its n elements
+    const uintptr_t src = (uintptr_t)d_coeffs, dst = (uintptr_t)d_out;
+    if (src != dst && src < dst + (32ull << (log_n + ext_bits)) &&
+        dst < src + (32ull << log_n)) {
+        set_err("ntt_extend: d_out overlaps d_coeffs without being equal");
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 om, g;
+    ff_from_bytes(om, omega_ext);
+    if (coset_gen) ff_from_bytes(g, coset_gen);
+    return ntt_extend_device(ctx, dev, (const fp256*)d_coeffs, log_n, ext_bits,
+                             (fp256*)d_out, om, coset_gen ? &g : nullptr);
+}
+
 int spectre_gpu_ntt_fr(spectre_gpu_ctx* ctx, uint8_t* data, uint32_t log_n,
                        const uint8_t omega[32], int inverse,
                        const uint8_t* coset_gen) {
@@ -550,6 +581,28 @@ int spectre_gpu_fr_vec_op(spectre_gpu_ctx* ctx, int dev, int op,
     return fr_vec_op_device(ctx, dev, op, (const fp256*)d_a,
                             (const fp256*)d_b, c ? &cv : nullptr,
                             (fp256*)d_out, n);
+}
+
+int spectre_gpu_fr_vec_mul_periodic(spectre_gpu_ctx* ctx, int dev,
+                                    const void* d_a, const uint8_t* table,
+                                    uint32_t period, void* d_out, uint64_t n) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_a || !d_out || !table) {
+        set_err("fr_vec_mul_periodic: null %s",
+                table ? "device pointer" : "table");
+        return -1;
+    }
+    if (period == 0 || (period & (period - 1)) ||
+        period > SPECTRE_VEC_PERIOD_MAX) {
+        set_err("fr_vec_mul_periodic: period %u is not a power of two in "
+                "[1, %u]", period, SPECTRE_VEC_PERIOD_MAX);
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 tab[SPECTRE_VEC_PERIOD_MAX];
+    for (uint32_t j = 0; j < period; j++) ff_from_bytes(tab[j], table + 32 * j);
+    return fr_vec_mul_periodic_device(ctx, dev, (const fp256*)d_a, tab, period,
+                                      (fp256*)d_out, n);
 }
 
 // ---------------------------------------------------------------- grand products

@@ -1,8 +1,9 @@
 // gate.hip — quotient-phase glue over Fr: the gate-expression evaluator and
-// the pointwise vector ops.
+// the pointwise vector ops, the periodic multiply of divide_by_vanishing_poly
+// among them.
 //
-// Both kernels compute in GateFr, Fr with the C CIOS multiply, the choice they
-// were written and measured under; neither has been timed with the asm
+// The kernels compute in GateFr, Fr with the C CIOS multiply, the choice they
+// were written and measured under; none has been timed with the asm
 // multiply.
 #include "internal.hpp"
 
@@ -199,6 +200,39 @@ int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
                        dim3(THREADS), 0, ds.stream, op, d_a, d_b, cv, d_out,
                        n);
+    HIP_TRY(hipStreamSynchronize(ds.stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- out[i] = a[i] * table[i mod period] (divide_by_vanishing_poly) -------
+// The table (at most 2 KiB) travels in the kernel arguments, filled to its
+// full length by repetition so the index needs only one mask. out may alias
+// a (hence no __restrict__): every thread reads its element before it writes.
+struct FrPeriodTable {
+    fp256 t[SPECTRE_VEC_PERIOD_MAX];
+};
+__global__ void k_fr_vec_mul_periodic(const fp256* a, FrPeriodTable table,
+                                      fp256* out, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fp256 r;
+    ff_mul<GateFr>(r, a[i], table.t[i & (SPECTRE_VEC_PERIOD_MAX - 1)]);
+    out[i] = r;
+}
+
+int fr_vec_mul_periodic_device(spectre_gpu_ctx* ctx, int dev,
+                               const fp256* d_a, const fp256* table,
+                               uint32_t period, fp256* d_out, uint64_t n) {
+    DeviceState& ds = ctx->devs[dev];
+    HIP_TRY(hipSetDevice(ds.device_id));
+    if (n == 0) return 0;
+    FrPeriodTable tab;
+    for (uint32_t j = 0; j < SPECTRE_VEC_PERIOD_MAX; j++)
+        tab.t[j] = table[j & (period - 1)];
+    hipLaunchKernelGGL(k_fr_vec_mul_periodic,
+                       dim3((uint32_t)((n + THREADS - 1) / THREADS)),
+                       dim3(THREADS), 0, ds.stream, d_a, tab, d_out, n);
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
     return 0;

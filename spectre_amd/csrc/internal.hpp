@@ -265,9 +265,22 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
 int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                      const fp256* d_b, const fp256* c, fp256* d_out,
                      uint64_t n);
+// gate.hip — out[i] = a[i] * table[i mod period], table = `period` host
+// elements, period a power of two <= SPECTRE_VEC_PERIOD_MAX (synchronizes).
+// d_out may alias d_a.
+int fr_vec_mul_periodic_device(spectre_gpu_ctx* ctx, int dev,
+                               const fp256* d_a, const fp256* table,
+                               uint32_t period, fp256* d_out, uint64_t n);
 // ntt.hip — in-place NTT on a device buffer (synchronizes the stream).
 int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
                const fp256& omega, int inverse, const fp256* coset_gen);
+// ntt.hip — forward (coset) NTT at 2^(log_n + ext_bits) of the 2^log_n
+// elements of d_coeffs followed by zeros, into d_out (synchronizes). d_out
+// is d_coeffs or does not overlap it; nothing behind the 2^log_n
+// coefficients is read. The caller has checked log_n + ext_bits <= 28.
+int ntt_extend_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
+                      uint32_t log_n, uint32_t ext_bits, fp256* d_out,
+                      const fp256& omega_ext, const fp256* coset_gen);
 
 // poly.hip — out[i] = in[i]^-1, zero staying zero (synchronizes). d_out may
 // alias d_in.

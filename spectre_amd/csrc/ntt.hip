@@ -36,6 +36,12 @@
 //   g^e = T1[e & 0xfff] * T2[e >> 12]   (one mul + two cached loads)
 // the omega ones built once per (omega, log_n) plan and cached on device.
 //
+// The extend transform (halo2's coeff_to_extended: 2^k coefficients, zeros up
+// to 2^(k+e), coset NTT there) is the same plan and pass loop at 2^(k+e) with
+// another first pass, the EXT instantiation of k_ntt_pass: it loads only the
+// coefficients and writes the result of the DIF levels that a zero operand
+// turns into a copy and one multiply (DESIGN.md "Extended domain").
+//
 // All Fr math is 8x32-limb Montgomery (ff.hpp); data stays in Montgomery form
 // end-to-end exactly as halo2 holds its &[Fr] slices.
 //
@@ -44,6 +50,7 @@
 // ms — register pressure at the 4-waves/SIMD occupancy these kernels need),
 // while it wins ~28% in the 256-thread MSM kernels. Measured r2.
 #include "internal.hpp"
+#include <type_traits>
 
 #ifdef SPECTRE_NTT_ASMMUL  // variant: re-tests the asm multiply under new
 using NttFr = Fr;          // block geometries
@@ -96,12 +103,17 @@ __global__ void k_pow_table(fp256 base, fp256* __restrict__ out,
 // when branched over at run time (measured 2^20 0.40 -> 0.46 ms with a
 // run-time flag), so the host launches the <true> instantiation only when
 // the tile gives every thread a quad (L >= 4*threads).
-template <bool R4>
+// SKIP (compile-time, the extend pass): the levels h = L/2 .. L >> skip are
+// already done, the load phase wrote their result; the remaining logL - skip
+// levels keep their twiddle strides, and their parity decides the lone
+// radix-2 level. Without SKIP, skip is not looked at.
+template <bool R4, bool SKIP>
 __device__ void lds_dif(uint4* lds4, uint32_t H, const fp256* __restrict__ twL,
-                        uint32_t logL) {
+                        uint32_t logL, uint32_t skip) {
     const uint32_t L = 1u << logL;
-    uint32_t h = L >> 1;
-    if (!R4 || (logL & 1))  // radix-2: all levels, or one to make pairs even
+    const uint32_t levels = SKIP ? logL - skip : logL;
+    uint32_t h = SKIP ? (L >> 1) >> skip : L >> 1;
+    if (!R4 || (levels & 1))  // radix-2: all levels, or one to make pairs even
     {
         for (; h >= 1; h >>= 1) {
             const uint32_t stride = (L >> 1) / h;
@@ -175,31 +187,79 @@ struct NttPass {
     uint32_t fin_logA, fin_logB;  // last pass: m = tA << fin_logB | tB
     uint32_t last, inverse;
 };
+// The first pass of an extend transform (EXT instantiations only, so the
+// plain instantiations keep the parent's kernel arguments): the input holds
+// 2^log_in elements and stands for 2^log_in coefficients followed by zeros.
+struct NttExtPass : NttPass {
+    uint32_t log_in;
+    uint32_t prune;  // min(ext_bits, logL): DIF levels done by the load phase
+};
 
 // in and out are the same buffer in a middle pass and in a single pass (hence
 // no __restrict__): a workgroup has its whole tile in LDS before it stores,
 // an in-place pass stores to the positions it loaded, and the last pass's
 // scatter runs in place only when its one workgroup is the whole transform.
-template <bool R4>
-__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(NttPass p) {
+//
+// EXT (compile-time, like R4: the plain instantiations must not pay for it)
+// is the first pass of an extend transform. Its input is 2^log_in elements
+// long and every index from there up counts as zero, so
+//   - in[pos] is loaded only where pos < 2^log_in: nothing behind the
+//     coefficients is ever read, which is all that correctness needs at any
+//     split, and what lets out alias in with an uninitialised tail;
+//   - tile elements s >= L' = L >> prune are zero, so each of the first
+//     `prune` DIF levels is a copy and one multiply: after them, block q
+//     (q < 2^prune) of the tile holds x[j] * root^(j * bitrev(q, prune)) at
+//     offset j < L'. The load phase writes that directly (root^e from twL,
+//     root^(L/2) = -1) and the butterflies start at level h = L'/2.
+template <bool R4, bool EXT = false>
+__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(
+    std::conditional_t<EXT, NttExtPass, NttPass> p) {
     extern __shared__ uint4 lds4[];
     const uint32_t L = 1u << p.logL;
     const uint32_t H = L;
     const uint32_t m = blockIdx.x;
     const uint32_t mS = m & ((1u << p.logS) - 1);
     const uint64_t base = ((uint64_t)(m >> p.logS) << (p.logL + p.logS)) + mS;
-    for (uint32_t s = threadIdx.x; s < L; s += blockDim.x) {
-        const uint64_t pos = base + ((uint64_t)s << p.logS);
-        fp256 v = p.in[pos];
-        if (p.cT1 && !p.inverse) {  // forward coset: g^(original index)
-            fp256 f;
-            tw_lookup(f, p.cT1, p.cT2, (uint32_t)pos);
-            ff_mul<NttFr>(v, v, f);
+    uint32_t skip = 0;
+    if constexpr (EXT) {
+        skip = p.prune;
+        const uint32_t Lp = L >> skip, half = L >> 1;
+        const uint64_t n_in = 1ull << p.log_in;
+        for (uint32_t s = threadIdx.x; s < Lp; s += blockDim.x) {
+            const uint64_t pos = base + ((uint64_t)s << p.logS);
+            fp256 v;
+            ff_set_zero(v);
+            if (pos < n_in) {
+                v = p.in[pos];
+                if (p.cT1) {  // forward coset: g^(original index)
+                    fp256 f;
+                    tw_lookup(f, p.cT1, p.cT2, (uint32_t)pos);
+                    ff_mul<NttFr>(v, v, f);
+                }
+            }
+            lds_split_st(lds4, s, H, v);
+            for (uint32_t q = 1; q < (1u << skip); q++) {
+                const uint32_t e = s * bitrev(q, skip);  // < L
+                fp256 t;
+                ff_mul<NttFr>(t, v, p.twL[e & (half - 1)]);
+                if (e & half) ff_neg<NttFr>(t, t);
+                lds_split_st(lds4, q * Lp + s, H, t);
+            }
         }
-        lds_split_st(lds4, s, H, v);
+    } else {
+        for (uint32_t s = threadIdx.x; s < L; s += blockDim.x) {
+            const uint64_t pos = base + ((uint64_t)s << p.logS);
+            fp256 v = p.in[pos];
+            if (p.cT1 && !p.inverse) {  // forward coset: g^(original index)
+                fp256 f;
+                tw_lookup(f, p.cT1, p.cT2, (uint32_t)pos);
+                ff_mul<NttFr>(v, v, f);
+            }
+            lds_split_st(lds4, s, H, v);
+        }
     }
     __syncthreads();
-    lds_dif<R4>(lds4, H, p.twL, p.logL);
+    lds_dif<R4, EXT>(lds4, H, p.twL, p.logL, skip);
     for (uint32_t s = threadIdx.x; s < L; s += blockDim.x) {
         const uint32_t t = bitrev(s, p.logL);
         fp256 v, f;
@@ -322,25 +382,36 @@ static int get_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
 // for tiny tiles where 64-thread blocks underutilize. Measured against L/1
 // and L/2: 2^22 coset 1.45 -> 1.19 ms, 2^23 fwd 2.54 -> 2.26, 2^24
 // unchanged, 2^20 within 4% of its best.
-static void launch_pass(hipStream_t st, const NttPass& pass, uint32_t log_n) {
+// ext_bits < 0: a plain pass. Otherwise the first pass of an extend transform
+// whose input is 2^(log_n - ext_bits) elements long.
+static void launch_pass(hipStream_t st, const NttPass& pass, uint32_t log_n,
+                        int ext_bits) {
     const uint32_t L = 1u << pass.logL;
     uint32_t threads = L / 4 > 128 ? L / 4 : 128;
     if (threads > NTT_THREADS) threads = NTT_THREADS;
-    // radix-4 instantiation only when every thread gets a quad
-    hipLaunchKernelGGL(L >= 4 * threads ? k_ntt_pass<true> : k_ntt_pass<false>,
-                       dim3(1u << (log_n - pass.logL)), dim3(threads),
-                       LDS_BYTES(L), st, pass);
+    const dim3 grid(1u << (log_n - pass.logL));
+    const bool r4 = L >= 4 * threads;  // only when every thread gets a quad
+    if (ext_bits < 0) {
+        hipLaunchKernelGGL(r4 ? k_ntt_pass<true> : k_ntt_pass<false>, grid,
+                           dim3(threads), LDS_BYTES(L), st, pass);
+        return;
+    }
+    NttExtPass ext;
+    static_cast<NttPass&>(ext) = pass;
+    ext.log_in = log_n - (uint32_t)ext_bits;
+    ext.prune = (uint32_t)ext_bits < pass.logL ? (uint32_t)ext_bits : pass.logL;
+    hipLaunchKernelGGL((r4 ? k_ntt_pass<true, true> : k_ntt_pass<false, true>),
+                       grid, dim3(threads), LDS_BYTES(L), st, ext);
 }
 
-int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
-               const fp256& omega, int inverse, const fp256* coset_gen) {
+// The pass loop of both entry points over 2^log_n elements (1 <= log_n <=
+// 28), d_in -> d_out. ext_bits < 0: d_in has 2^log_n elements (and is d_out,
+// for the in-place call). ext_bits >= 0: forward only; d_in has
+// 2^(log_n - ext_bits) elements, zeros follow.
+static int ntt_run(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
+                   fp256* d_out, uint32_t log_n, int ext_bits,
+                   const fp256& omega, int inverse, const fp256* coset_gen) {
     DeviceState& ds = ctx->devs[dev];
-    HIP_TRY(hipSetDevice(ds.device_id));
-    if (log_n > 28) {  // BN254 Fr 2-adicity
-        set_err("ntt: log_n %u > 28 unsupported (Fr 2-adicity)", log_n);
-        return -3;
-    }
-    if (log_n == 0) return 0;  // DFT of size 1 is the identity; n^{-1} = 1, g^0 = 1
     const uint32_t n = 1u << log_n;
     NttPlan* plan = nullptr;
     RC_TRY(get_plan(ds, omega, log_n, ctx->ntt_force3, &plan));
@@ -359,12 +430,12 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
         ff_to_mont<NttFr>(nm, ncanon);
         ff_inv<NttFr>(pass.scale, nm);
     }
-    // data -> tmp, tmp in place, tmp -> data; a single pass runs on data
+    // in -> tmp, tmp in place, tmp -> out; a single pass runs in -> out
     uint32_t done = 0;  // log sizes of the axes already transformed
     for (uint32_t i = 0; i < plan->npass; i++) {
         const bool first = i == 0, last = i == plan->npass - 1;
-        pass.in = first ? d_data : tmp;
-        pass.out = last ? d_data : tmp;
+        pass.in = first ? d_in : tmp;
+        pass.out = last ? d_out : tmp;
         pass.twL = plan->tw[i].ptr;
         pass.logL = plan->k[i];
         pass.logS = log_n - done - plan->k[i];
@@ -377,10 +448,38 @@ int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
         const bool coset = coset_gen && (inverse ? last : first);
         pass.cT1 = coset ? ds.d_cosetA.ptr : nullptr;
         pass.cT2 = coset ? ds.d_cosetA.ptr + plan->t1n : nullptr;
-        launch_pass(ds.stream, pass, log_n);
+        launch_pass(ds.stream, pass, log_n, first ? ext_bits : -1);
         done += plan->k[i];
     }
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
+               const fp256& omega, int inverse, const fp256* coset_gen) {
+    HIP_TRY(hipSetDevice(ctx->devs[dev].device_id));
+    if (log_n > 28) {  // BN254 Fr 2-adicity
+        set_err("ntt: log_n %u > 28 unsupported (Fr 2-adicity)", log_n);
+        return -3;
+    }
+    if (log_n == 0) return 0;  // DFT of size 1 is the identity; n^{-1} = 1, g^0 = 1
+    return ntt_run(ctx, dev, d_data, d_data, log_n, -1, omega, inverse,
+                   coset_gen);
+}
+
+int ntt_extend_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
+                      uint32_t log_n, uint32_t ext_bits, fp256* d_out,
+                      const fp256& omega_ext, const fp256* coset_gen) {
+    DeviceState& ds = ctx->devs[dev];
+    HIP_TRY(hipSetDevice(ds.device_id));
+    if (log_n + ext_bits == 0) {  // one element, g^0 = 1: a copy
+        if (d_out != d_coeffs)
+            HIP_TRY(hipMemcpyAsync(d_out, d_coeffs, sizeof(fp256),
+                                   hipMemcpyDeviceToDevice, ds.stream));
+        HIP_TRY(hipStreamSynchronize(ds.stream));
+        return 0;
+    }
+    return ntt_run(ctx, dev, d_coeffs, d_out, log_n + ext_bits, (int)ext_bits,
+                   omega_ext, 0, coset_gen);
 }

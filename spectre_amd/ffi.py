@@ -132,6 +132,16 @@ def load_library() -> ctypes.CDLL:
         c.c_void_p, c.c_int, c.c_void_p, c.c_uint32, c.c_void_p, c.c_int,
         c.c_void_p,
     ]
+    lib.spectre_gpu_ntt_fr_extend_device.restype = c.c_int
+    lib.spectre_gpu_ntt_fr_extend_device.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p,
+        c.c_void_p, c.c_void_p,
+    ]
+    lib.spectre_gpu_fr_vec_mul_periodic.restype = c.c_int
+    lib.spectre_gpu_fr_vec_mul_periodic.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p,
+        c.c_uint64,
+    ]
     lib.spectre_gpu_fr_vec_op.restype = c.c_int
     lib.spectre_gpu_fr_vec_op.argtypes = [
         c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
@@ -429,6 +439,23 @@ class SpectreGpu:
             1 if inverse else 0, cg)
         self._check(rc, "ntt_fr_device")
 
+    def ntt_extend_device(self, d_coeffs: int, log_n: int, ext_bits: int,
+                          d_out: int, omega_ext: bytes,
+                          coset_gen: bytes | None = None,
+                          dev: int = 0) -> None:
+        """halo2's coeff_to_extended: the forward (coset) NTT at
+        2^(log_n + ext_bits), root omega_ext, of the 2^log_n coefficients at
+        d_coeffs followed by zeros, into the 2^(log_n + ext_bits) elements at
+        d_out. d_out may equal d_coeffs; the elements behind the coefficients
+        are never read. Otherwise the two must not overlap."""
+        om = (ctypes.c_uint8 * 32).from_buffer_copy(omega_ext)
+        cg = ((ctypes.c_uint8 * 32).from_buffer_copy(coset_gen)
+              if coset_gen else None)
+        rc = self._lib.spectre_gpu_ntt_fr_extend_device(
+            self._ctx, dev, ctypes.c_void_p(d_coeffs), log_n, ext_bits,
+            ctypes.c_void_p(d_out), om, cg)
+        self._check(rc, "ntt_fr_extend_device")
+
     # gate-expression evaluator opcodes (spectre_gpu.h)
     GATE_COL, GATE_CONST, GATE_ADD, GATE_SUB, GATE_MUL, GATE_NEG = range(6)
 
@@ -464,6 +491,22 @@ class SpectreGpu:
             ctypes.c_void_p(d_b) if d_b else None, cc,
             ctypes.c_void_p(d_out), n)
         self._check(rc, "fr_vec_op")
+
+    VEC_PERIOD_MAX = 64  # = SPECTRE_VEC_PERIOD_MAX
+
+    def fr_vec_mul_periodic(self, d_a: int, table: bytes, d_out: int, n: int,
+                            dev: int = 0) -> None:
+        """d_out[i] = d_a[i] * table[i mod period] over n Montgomery Fr
+        elements (halo2's divide_by_vanishing_poly with table =
+        t_evaluations); period = len(table) / 32, a power of two up to
+        VEC_PERIOD_MAX. d_out may equal d_a."""
+        assert len(table) % 32 == 0
+        tab = (ctypes.c_uint8 * max(32, len(table))).from_buffer_copy(
+            table.ljust(32, b"\0"))
+        rc = self._lib.spectre_gpu_fr_vec_mul_periodic(
+            self._ctx, dev, ctypes.c_void_p(d_a), tab, len(table) // 32,
+            ctypes.c_void_p(d_out), n)
+        self._check(rc, "fr_vec_mul_periodic")
 
     def fr_batch_invert(self, d_in: int, d_out: int, n: int,
                         dev: int = 0) -> None:

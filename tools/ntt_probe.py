@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """NTT timing probe (GPU box): device-resident forward/inverse/coset NTT at
-the BASELINE sizes. Not part of the bench contract — a tuning tool."""
+the BASELINE sizes, and the zero-padded coset NTT (extend) from a quarter of
+each size. Not part of the bench contract — a tuning tool."""
 import argparse
 import hashlib
 import os
@@ -14,6 +15,7 @@ import pywrap as oracle  # noqa: E402
 from spectre_amd import SpectreGpu  # noqa: E402
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+EXT_BITS = 2  # the pinned circuits' extended_k - k
 
 
 def omega_for(log_n):
@@ -33,8 +35,9 @@ def main():
                          "size separated by commas (default 10)")
     ap.add_argument("--hash", action="store_true",
                     help="also print the sha256 of the downloaded output of "
-                         "one forward, one inverse and one coset call per "
-                         "size, each on the freshly uploaded input")
+                         "one forward, one inverse, one coset and one "
+                         "extend call per size, each on the freshly uploaded "
+                         "input")
     args = ap.parse_args()
     reps_list = [int(r) for r in args.reps.split(",")]
     if len(reps_list) == 1:
@@ -72,6 +75,25 @@ def main():
             print(f"2^{log_n} {name}: {dt:7.3f} ms  "
                   f"({2 * gb / dt * 1e3:7.1f} GB/s algorithmic 2-pass)"
                   f"  x{reps}")
+        if log_n >= EXT_BITS:
+            # extend: 2^(log_n - 2) coefficients -> the same 2^log_n coset
+            # domain, in place; what a call leaves in the first quarter is
+            # the next call's input
+            if args.hash:
+                gpu.upload(d, data[:32 * (n >> EXT_BITS)])
+                gpu.ntt_extend_device(d, log_n - EXT_BITS, EXT_BITS, d, w,
+                                      coset_gen=g)
+                h = hashlib.sha256(gpu.download(d, 32 * n)).hexdigest()
+                print(f"2^{log_n} extend sha256 {h}")
+            gpu.ntt_extend_device(d, log_n - EXT_BITS, EXT_BITS, d, w,
+                                  coset_gen=g)  # warm
+            t0 = time.time()
+            for _ in range(reps):
+                gpu.ntt_extend_device(d, log_n - EXT_BITS, EXT_BITS, d, w,
+                                      coset_gen=g)
+            dt = (time.time() - t0) / reps * 1e3
+            print(f"2^{log_n} extend: {dt:7.3f} ms  "
+                  f"(2^{log_n - EXT_BITS} coefficients in place)  x{reps}")
         gpu.free(d)
     gpu.close()
 
