@@ -30,7 +30,8 @@
  * deliberately no CPU fallback — a missing GPU fails loudly); the only
  * host-only entry points are spectre_gpu_msm_g1_combine(_windows),
  * spectre_gpu_msm_acc_auto_entries, spectre_gpu_msm_fold_window,
- * spectre_gpu_fr_scan_tile_default and the format/version queries.
+ * spectre_gpu_fr_scan_tile_default, spectre_gpu_ntt_split and the
+ * format/version queries.
  */
 #ifndef SPECTRE_GPU_H
 #define SPECTRE_GPU_H
@@ -192,6 +193,12 @@ int spectre_gpu_ntt_fr(spectre_gpu_ctx*, uint8_t* data, uint32_t log_n,
 int spectre_gpu_ntt_fr_device(spectre_gpu_ctx*, int dev, void* d_data,
                               uint32_t log_n, const uint8_t omega[32],
                               int inverse, const uint8_t* coset_gen);
+/* The rule that splits a 2^log_n transform into passes (host-only, pure;
+ * tests): k[0 .. count) receive the axis log sizes in pass order, each in
+ * 1..12 and summing to log_n, the rest of k is zeroed, and the pass count
+ * (1..3) is returned. force3 != 0 is the rule a context created under
+ * SPECTRE_NTT_FORCE3 follows. Returns 0 for log_n == 0 or log_n > 28. */
+uint32_t spectre_gpu_ntt_split(uint32_t log_n, int force3, uint32_t k[3]);
 /* out[t] = sum_{i < n} a[i] * coset_gen^i * omega_ext^(i*t),  t < N,
  * n = 2^log_n, N = 2^(log_n + ext_bits): halo2's coeff_to_extended
  * (distribute_powers_zeta, resize with zeros, best_fft at extended_k).

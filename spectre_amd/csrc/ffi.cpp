@@ -482,6 +482,12 @@ int spectre_gpu_msm_g1(spectre_gpu_ctx* ctx, uint64_t bases_id,
 }
 
 // ---------------------------------------------------------------- NTT
+uint32_t spectre_gpu_ntt_split(uint32_t log_n, int force3, uint32_t k[3]) {
+    if (log_n == 0 || log_n > 28 || !k) return 0;
+    k[0] = k[1] = k[2] = 0;
+    return ntt_split(log_n, force3 != 0, k);
+}
+
 int spectre_gpu_ntt_fr_device(spectre_gpu_ctx* ctx, int dev, void* d_data,
                               uint32_t log_n, const uint8_t omega[32],
                               int inverse, const uint8_t* coset_gen) {

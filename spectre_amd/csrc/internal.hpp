@@ -271,6 +271,9 @@ int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
 int fr_vec_mul_periodic_device(spectre_gpu_ctx* ctx, int dev,
                                const fp256* d_a, const fp256* table,
                                uint32_t period, fp256* d_out, uint64_t n);
+// ntt.hip — the axis log sizes k[0..npass) of a 2^log_n transform, 1 <=
+// log_n <= 28 (pure; host). Returns npass.
+uint32_t ntt_split(uint32_t log_n, bool force3, uint32_t k[3]);
 // ntt.hip — in-place NTT on a device buffer (synchronizes the stream).
 int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
                const fp256& omega, int inverse, const fp256* coset_gen);

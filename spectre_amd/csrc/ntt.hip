@@ -287,8 +287,9 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(
 // ---------------------------------------------------------------- host side
 // Axis log sizes k[0..npass) for n = 2^log_n (log_n >= 1), each <= 12; the
 // last axis is the contiguous one. Returns npass. force3 takes the three-axis
-// rule at sizes that do not need it (testing).
-static uint32_t ntt_split(uint32_t log_n, bool force3, uint32_t k[3]) {
+// rule at sizes that do not need it (testing). Pure; exported as
+// spectre_gpu_ntt_split so that tests can pin the rule.
+uint32_t ntt_split(uint32_t log_n, bool force3, uint32_t k[3]) {
     if (log_n > 24 || (force3 && log_n >= 3)) {
         // k[0] = 12 gives the first pass 4096-element tiles (radix-4
         // rounds): measured -6% at 2^26 against the balanced split, neutral

@@ -132,6 +132,10 @@ def load_library() -> ctypes.CDLL:
         c.c_void_p, c.c_int, c.c_void_p, c.c_uint32, c.c_void_p, c.c_int,
         c.c_void_p,
     ]
+    lib.spectre_gpu_ntt_split.restype = c.c_uint32
+    lib.spectre_gpu_ntt_split.argtypes = [
+        c.c_uint32, c.c_int, c.POINTER(c.c_uint32),
+    ]
     lib.spectre_gpu_ntt_fr_extend_device.restype = c.c_int
     lib.spectre_gpu_ntt_fr_extend_device.argtypes = [
         c.c_void_p, c.c_int, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p,
@@ -222,6 +226,15 @@ def fr_scan_tile_default() -> int:
     """Host-only: the built-in elements per workgroup tile of
     fr_batch_invert / fr_grand_product (see set_fr_scan_tile)."""
     return load_library().spectre_gpu_fr_scan_tile_default()
+
+
+def ntt_split(log_n: int, force3: bool = False) -> tuple[int, ...]:
+    """Host-only: the axis log sizes, in pass order, into which the library
+    splits a 2^log_n NTT (force3: under SPECTRE_NTT_FORCE3). Empty for
+    log_n == 0 and log_n > 28."""
+    k = (ctypes.c_uint32 * 3)()
+    count = load_library().spectre_gpu_ntt_split(log_n, 1 if force3 else 0, k)
+    return tuple(k[:count])
 
 
 def combine_window_partials(partials: bytes, nshards: int) -> bytes:

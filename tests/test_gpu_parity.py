@@ -571,6 +571,10 @@ print("ntt legs ok")
     assert "ntt legs ok" in r.stdout, r.stdout + r.stderr
 
 
+# sizes of the forced three-pass test (test_ntt_split.py reads the list)
+FORCE3_LOG_NS = (3, 4, 5, 7, 6, 10, 12, 14)
+
+
 def test_ntt_three_pass_forced_vs_oracle(oracle, golden):
     """The 3-pass (log_n>24) path, forced at oracle-checkable sizes via
     SPECTRE_NTT_FORCE3, must match the oracle bit-exactly (fwd/inv/coset,
@@ -578,7 +582,7 @@ def test_ntt_three_pass_forced_vs_oracle(oracle, golden):
     (1,1,1), (2,1,1), (2,2,1), (3,2,2): one-entry twiddle tables and unequal
     axes."""
     _ntt_legs_vs_oracle_in_child({"SPECTRE_NTT_FORCE3": "1"},
-                                 (3, 4, 5, 7, 6, 10, 12, 14))
+                                 FORCE3_LOG_NS)
 
 
 def test_ntt_two_pass_short_first_axis_vs_oracle(oracle, golden):
