@@ -33,8 +33,14 @@ struct fp256 {
 // against tests/golden fixtures; see tests/golden/bn254_ref.py).
 // kAsmMul: which multiply ff_mul<C> is in device code, the asm column form
 // (true) or the compiled CIOS (false). The host always runs the CIOS.
+// kChainAddSub: which form ff_add / ff_sub / ff_cond_sub_mod take, host and
+// device: branch-free 32-bit carry chains with the correction selected by a
+// mask (true), or 64-bit limb arithmetic with the correction behind a branch
+// (false). Same bytes either way; the choice is per field because it moves
+// register allocation in opposite directions (see "add / sub / reduce" below).
 struct FqP {
     static constexpr bool kAsmMul = true;
+    static constexpr bool kChainAddSub = true;
     FF_HD static constexpr uint32_t mod(int i) {
         constexpr uint32_t M[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
                                    0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
@@ -54,6 +60,7 @@ struct FqP {
 };
 struct FrP {
     static constexpr bool kAsmMul = true;
+    static constexpr bool kChainAddSub = false;
     FF_HD static constexpr uint32_t mod(int i) {
         constexpr uint32_t M[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u,
                                    0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
@@ -75,6 +82,7 @@ struct FrP {
 // measured faster with it (ntt.hip, gate.hip).
 struct FrCios : FrP {
     static constexpr bool kAsmMul = false;
+    static constexpr bool kChainAddSub = false;
 };
 
 // ---- generic ops ------------------------------------------------------------
@@ -119,8 +127,53 @@ FF_HD uint32_t ff_add_raw(fp256& o, const fp256& a, const fp256& b) {
     }
     return (uint32_t)c;
 }
+// ---- add / sub / reduce -----------------------------------------------------
+// Two forms, chosen by C::kChainAddSub, that return the same bytes.
+// The 64-bit form compiles on gfx950 to v_sub_co + v_subb_co + v_ashrrev +
+// v_mov + v_lshl_add_u64 per limb and puts the correction behind a branch; the
+// borrow differs per lane, so a wave issues both sides: ff_sub<Fq> is about 75
+// issue slots. The chain form is v_sub_co / v_subb_co once per limb and the
+// correction added under a mask, about 24. In the point formulas of the MSM
+// kernels (Fq) that is a third of all vector instructions and frees about 50
+// VGPRs (profiles/field_chain_kernel_resources.txt). The NTT and gate kernels
+// (FrCios) go the other way under the chain form, to 128 VGPRs and scratch,
+// so they keep the 64-bit form.
+FF_HD uint32_t ff_adc_(uint32_t a, uint32_t b, uint32_t& carry) {
+#if defined(__has_builtin) && __has_builtin(__builtin_addc)
+    unsigned out;
+    const uint32_t r = __builtin_addc(a, b, carry, &out);
+    carry = out;
+    return r;
+#else
+    const uint64_t s = (uint64_t)a + b + carry;
+    carry = (uint32_t)(s >> 32);
+    return (uint32_t)s;
+#endif
+}
+FF_HD uint32_t ff_sbb_(uint32_t a, uint32_t b, uint32_t& borrow) {
+#if defined(__has_builtin) && __has_builtin(__builtin_subc)
+    unsigned out;
+    const uint32_t r = __builtin_subc(a, b, borrow, &out);
+    borrow = out;
+    return r;
+#else
+    const uint64_t d = (uint64_t)a - b - borrow;
+    borrow = (uint32_t)(d >> 32) & 1;
+    return (uint32_t)d;
+#endif
+}
+// o -= m where extra (bit 256 of o) is set or o >= m: a trial subtract, kept
+// iff extra || no borrow
+template <class C> FF_HD void ff_cond_sub_mod_chain_(fp256& o, uint32_t extra) {
+    uint32_t d[8], brw = 0;
+    for (int i = 0; i < 8; i++) d[i] = ff_sbb_(o.l[i], C::mod(i), brw);
+    const bool keep = extra != 0 || brw == 0;
+    for (int i = 0; i < 8; i++) o.l[i] = keep ? d[i] : o.l[i];
+}
 template <class C> FF_HD void ff_cond_sub_mod(fp256& o, uint32_t extra) {
-    if (extra || ff_geq_mod<C>(o)) {
+    if constexpr (C::kChainAddSub) {
+        ff_cond_sub_mod_chain_<C>(o, extra);
+    } else if (extra || ff_geq_mod<C>(o)) {
         uint64_t brw = 0;
         for (int i = 0; i < 8; i++) {
             uint64_t d = (uint64_t)o.l[i] - C::mod(i) - brw;
@@ -130,11 +183,23 @@ template <class C> FF_HD void ff_cond_sub_mod(fp256& o, uint32_t extra) {
     }
 }
 template <class C> FF_HD void ff_add(fp256& o, const fp256& a, const fp256& b) {
-    uint32_t c = ff_add_raw(o, a, b);
-    ff_cond_sub_mod<C>(o, c);
+    if constexpr (C::kChainAddSub) {
+        uint32_t c = 0;
+        for (int i = 0; i < 8; i++) o.l[i] = ff_adc_(a.l[i], b.l[i], c);
+        ff_cond_sub_mod_chain_<C>(o, c);
+    } else {
+        uint32_t c = ff_add_raw(o, a, b);
+        ff_cond_sub_mod<C>(o, c);
+    }
 }
 template <class C> FF_HD void ff_sub(fp256& o, const fp256& a, const fp256& b) {
-    if (ff_sub_raw(o, a, b)) {
+    if constexpr (C::kChainAddSub) {
+        uint32_t brw = 0;
+        for (int i = 0; i < 8; i++) o.l[i] = ff_sbb_(a.l[i], b.l[i], brw);
+        const uint32_t mask = 0u - brw;  // add m back iff the chain borrowed
+        uint32_t c = 0;
+        for (int i = 0; i < 8; i++) o.l[i] = ff_adc_(o.l[i], C::mod(i) & mask, c);
+    } else if (ff_sub_raw(o, a, b)) {
         uint64_t c = 0;
         for (int i = 0; i < 8; i++) {
             c += (uint64_t)o.l[i] + C::mod(i);
@@ -272,6 +337,87 @@ __device__ __forceinline__ void ff_mul_cols(fp256& o, const fp256& A,
     // rather than truncating silently.
     ff_cond_sub_mod<C>(o, (uint32_t)(acc >> 32));
 }
+
+// ---- device squaring: the column form with 36 products instead of 64 -------
+// With B = 2^32 and T_i = sum_{j>i} a_j B^j,
+//   a^2 = sum_i a_i^2 B^(2i) + sum_i a_i (2 T_i).
+// 2 T_i has the limbs D(i,j), j = i+1 .. 7:
+//   D(i,j)   = (a_j << 1) | (a_(j-1) >> 31)   for j > i + 1   (dbl[j])
+//   D(i,i+1) =  a_(i+1) << 1                                  (adj[i+1])
+// adj has its low bit clear because limb i is not part of T_i, and nothing is
+// lost at the top while a < 2^255 (a_7 >> 31 == 0): true of every reduced
+// element of a field whose modulus is below 2^255, false at 2^256 - 1. Column
+// K gets a_i D(i, K-i) for 2i < K and a_(K/2)^2 for even K; the m_k products,
+// the (acc, ovf) scheme and the one-product asm blocks are those of
+// ff_mul_cols, and so are the result bytes.
+template <int K>
+__device__ __forceinline__ void detail_ff_sqr_col(uint64_t& acc, uint32_t& ovf,
+                                                  const uint32_t* a,
+                                                  const uint32_t* adj,
+                                                  const uint32_t* dbl) {
+#pragma unroll
+    for (int i = K < 8 ? 0 : K - 7; 2 * i + 1 < K; i++)
+        ff_mad64_(acc, ovf, a[i], dbl[K - i]);
+    if constexpr (K % 2) ff_mad64_(acc, ovf, a[K / 2], adj[K / 2 + 1]);
+    else ff_mad64_(acc, ovf, a[K / 2], a[K / 2]);
+}
+template <class C, int K>
+__device__ __forceinline__ void detail_ff_sqr_low_cols(uint64_t& acc,
+                                                       uint32_t& ovf,
+                                                       const uint32_t* a,
+                                                       const uint32_t* adj,
+                                                       const uint32_t* dbl,
+                                                       uint32_t* m) {
+    if constexpr (K < 8) {
+        detail_ff_sqr_col<K>(acc, ovf, a, adj, dbl);
+#pragma unroll
+        for (int i = 0; i < K; i++) ff_mad64_s_(acc, ovf, m[i], C::mod(K - i));
+        m[K] = (uint32_t)acc * C::inv();
+        ff_mad64_s_(acc, ovf, m[K], C::mod(0));
+        acc = (acc >> 32) | ((uint64_t)ovf << 32);
+        ovf = 0;
+        detail_ff_sqr_low_cols<C, K + 1>(acc, ovf, a, adj, dbl, m);
+    }
+}
+template <class C, int K>
+__device__ __forceinline__ void detail_ff_sqr_high_cols(uint64_t& acc,
+                                                        uint32_t& ovf,
+                                                        const uint32_t* a,
+                                                        const uint32_t* adj,
+                                                        const uint32_t* dbl,
+                                                        const uint32_t* m,
+                                                        uint32_t* out) {
+    if constexpr (K < 15) {
+        detail_ff_sqr_col<K>(acc, ovf, a, adj, dbl);
+#pragma unroll
+        for (int i = K - 7; i < 8; i++) ff_mad64_s_(acc, ovf, m[i], C::mod(K - i));
+        out[K - 8] = (uint32_t)acc;
+        acc = (acc >> 32) | ((uint64_t)ovf << 32);
+        ovf = 0;
+        detail_ff_sqr_high_cols<C, K + 1>(acc, ovf, a, adj, dbl, m, out);
+    }
+}
+template <class C>
+__device__ __forceinline__ void ff_sqr_cols(fp256& o, const fp256& A) {
+    static_assert(C::mod(7) < 0x80000000u,
+                  "the doubled limbs drop bit 255: reduced elements must be "
+                  "below 2^255");
+    uint32_t a[8], adj[8], dbl[8], m[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) a[i] = A.l[i];  // o may be A
+    adj[0] = dbl[0] = 0;                        // never read
+#pragma unroll
+    for (int j = 1; j < 8; j++) {
+        adj[j] = a[j] << 1;
+        dbl[j] = (a[j] << 1) | (a[j - 1] >> 31);
+    }
+    uint64_t acc = 0;
+    uint32_t ovf = 0;
+    detail_ff_sqr_low_cols<C, 0>(acc, ovf, a, adj, dbl, m);
+    detail_ff_sqr_high_cols<C, 8>(acc, ovf, a, adj, dbl, m, o.l);
+    o.l[7] = (uint32_t)acc;
+    ff_cond_sub_mod<C>(o, (uint32_t)(acc >> 32));
+}
 #endif
 
 // The one multiply: the form the field names on the device, CIOS on the host.
@@ -285,7 +431,17 @@ template <class C> FF_HD void ff_mul(fp256& o, const fp256& a, const fp256& b) {
     ff_mul_cios<C>(o, a, b);
 }
 
-template <class C> FF_HD void ff_sqr(fp256& o, const fp256& a) { ff_mul<C>(o, a, a); }
+// The one squaring: where the field multiplies with the asm column form, the
+// column squaring; ff_mul(a, a) elsewhere. a must be reduced (a < m).
+template <class C> FF_HD void ff_sqr(fp256& o, const fp256& a) {
+#if defined(FF_HAVE_ASM_MUL)
+    if constexpr (C::kAsmMul) {
+        ff_sqr_cols<C>(o, a);
+        return;
+    }
+#endif
+    ff_mul<C>(o, a, a);
+}
 
 // Montgomery conversion
 template <class C> FF_HD void ff_to_mont(fp256& o, const fp256& a_canon) {

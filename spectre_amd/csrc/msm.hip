@@ -39,9 +39,11 @@
 // batch with the window Horner (~255 doublings + adds) and one field
 // inversion to affine.
 //
-// All field math is 8x32-limb Montgomery CIOS (ff.hpp) — VALU integer work
-// (measured at the chip's v_mad_u64_u32 issue ceiling); MFMA does not apply
-// to modular arithmetic.
+// All field math is 8x32-limb Montgomery (ff.hpp: the asm column multiply and
+// squaring, add/sub/reduce as carry chains) — VALU integer work, issue-bound:
+// in k_bucket_acc 2 057 of 6 229 vector instructions are v_mad_u64_u32 and as
+// many their carry adds (field add/sub section); MFMA does not
+// apply to modular arithmetic.
 #include "internal.hpp"
 #include <hipcub/hipcub.hpp>
 
@@ -51,16 +53,20 @@
 // spills to scratch. Allowing 2 waves/SIMD (256 VGPR) removes the spills —
 // latency hiding comes from the serial-add structure, not occupancy
 // (measured: 1 add-chain/thread already saturates the VALU issue pipe).
+// With the carry-chain add/sub the kernels need 117-155 VGPRs (221 before)
+// and run at 3-4 waves/SIMD under the same bound
+// (profiles/field_chain_kernel_resources.txt).
 #define PT_KERNEL __global__ __launch_bounds__(THREADS, 2)
 // The accumulate/fix kernels have no barriers (k_bucket_acc's LDS staging
 // is private to each wave, 8 KiB), so their block size only sets the
 // residency granule. MEASURED (r2): 64/128/256-thread blocks
 // are within run-to-run noise (acc 2.26-2.29 ms). The code object says
-// k_bucket_acc uses 165 VGPRs (168 allocated, 3 waves/SIMD; 163 before the
-// LDS-staged prefetch) — the profiler's VGPR column shows half the
-// allocation (84), which earlier notes misread as 4-5 waves/SIMD. One madd
-// chain per SIMD already fills the multiply issue pipe, so neither block
-// size nor residency moves the stage. Kept tunable.
+// k_bucket_acc uses 111 VGPRs (4 waves/SIMD; four blocks stage 128 KiB of a
+// CU's 160 KiB of LDS). It had 165 (3 waves/SIMD) while ff_add / ff_sub were
+// 64-bit limb code behind branches — the profiler's VGPR column shows half
+// the allocation, which earlier notes misread as 4-5 waves/SIMD. One madd
+// chain per SIMD already fills the issue pipe, so neither block size nor
+// residency moves the stage. Kept tunable.
 #ifndef MSM_ACC_THREADS
 #define MSM_ACC_THREADS 256
 #endif
@@ -147,7 +153,8 @@ __global__ void k_bucket_offsets(const uint32_t* __restrict__ keys,
 //
 // The entry stream is software-pipelined through LDS, so no global load sits
 // between two madds and the prefetched data costs no registers (holding the
-// next point in VGPRs across the madd drops the kernel to 2 waves/SIMD):
+// next point in VGPRs across the madd dropped the 165-VGPR kernel to 2
+// waves/SIMD; not retried at 111):
 //   * keys/values arrive in 16-byte quads (thread ranges start at multiples
 //     of 4 entries, so every quad is aligned), double-buffered: the quad
 //     after the current one is in flight while the current one is consumed;
@@ -346,7 +353,8 @@ PT_KERNEL void k_window_chunks(const g1_jac* __restrict__ buckets,
 // takes the stage from 0.74 to 0.61 ms at every n and one synchronous call
 // at n = 2^12 from 1.42 to 1.31 ms; the pipelined throughput at n = 2^20 is
 // the same within its noise. 512 threads is two waves on each SIMD of a CU,
-// the 256-VGPR budget the kernel needs (220).
+// within the 256-VGPR budget (the kernel has 143 VGPRs, 220 before the
+// carry-chain add/sub).
 #ifndef WSUM_THREADS
 #define WSUM_THREADS 512
 #endif
@@ -408,7 +416,7 @@ __global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_tail(
 // ---- host orchestration ---------------------------------------------------
 // Entries per accumulate thread when the caller has not fixed one.
 // MEASURED on MI355X (n = 2^20, accumulate + fix stage): one madd chain per
-// SIMD already fills the integer-multiply issue pipe, so the stage costs the
+// SIMD already fills the issue pipe, so the stage costs the
 // same 2.23-2.25 ms for E = 32, 44, 64 whether or not the grid is a whole
 // number of resident rounds, and MORE for one exact round (E = 88: 2.38 ms;
 // half a round, E = 176: 3.16 ms): the dispatcher balances many short
@@ -417,6 +425,10 @@ __global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_tail(
 // stage takes 0.91 ms at E = 64 (64 blocks on 256 CUs), 0.52 at 32, 0.32 at
 // 16, 0.29 at 8 and 0.37 at 4, where the two boundary partials per thread
 // that k_bucket_fix merges start to cost more than the parallelism gives.
+// Measured again with the carry-chain add/sub (every figure about a fifth
+// lower, the same ordering: 1.85 / 1.87 / 1.96 ms at E = 64 / 32 / 88;
+// 0.70 / 0.40 / 0.24 / 0.24 / 0.27 at n = 2^16): the rule stands
+// (profiles/field_chain_sweeps.txt).
 // The rule: aim for MSM_ACC_TARGET_BLOCKS resident blocks on every CU
 // (fewer if fewer fit), E rounded up to the quad the kernel loads, within
 // [MSM_ACC_E_MIN, MSM_ACC_E_MAX].
