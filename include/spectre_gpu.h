@@ -2,7 +2,8 @@
  * Besides the two transforms it carries the per-column stages that keep a
  * proof's polynomials on the device between them: gate evaluation and vector
  * ops (quotient phase), batch inverse and grand product (Z columns), the
- * lookup argument's sorted input and permuted table columns, and polynomial
+ * lookup argument's sorted input and permuted table columns, the permutation
+ * argument's grand-product terms and row-power columns, and polynomial
  * evaluation and (X - z) division (opening phase).
  *
  * This is the drop-in boundary for the Spectre/halo2 proving hot path: the
@@ -343,6 +344,39 @@ int spectre_gpu_fr_lookup_permute(spectre_gpu_ctx*, int dev,
                                   const void* d_input, const void* d_table,
                                   void* d_input_perm, void* d_table_perm,
                                   uint64_t u);
+
+/* ---- permutation argument (device buffers, Montgomery Fr) ----------------
+ * halo2's permutation::prover::commit builds each Z column from per-row
+ * products that need omega^i, and the extended-domain permutation constraint
+ * needs X_i = zeta * omega_ext^i. These two calls make both on device `dev`;
+ * they synchronize. A permutation Z column is then
+ *   permutation_terms -> fr_grand_product(num, den, z0 = the previous
+ *   chunk's out_last) over the usable rows,
+ * chunks chaining through out_last and delta0 <- delta0 * delta^m; the
+ * constraint is an fr_gate_eval program over one extra column,
+ * fr_powers(zeta, omega_ext, 2^extended_k), built once per domain. */
+/* out[i] = c * g^i, i < n.  c == NULL: one.  g, c: host, 32 B Montgomery Fr,
+ * any field elements (g need not be a root of unity; g = 0 gives c,0,0,...).
+ * n == 0: nothing is done. n <= 2^28. */
+int spectre_gpu_fr_powers(spectre_gpu_ctx*, int dev, const uint8_t c[32],
+                          const uint8_t g[32], void* d_out, uint64_t n);
+
+#define SPECTRE_PERM_MAX_COLS 8u
+/* One chunk of halo2's permutation::prover::commit, rows 0..n:
+ *   den[i] = prod_{j<m} (values[j][i] + beta*sigmas[j][i]          + gamma)
+ *   num[i] = prod_{j<m} (values[j][i] + beta*delta0*delta^j*omega^i + gamma)
+ * d_values, d_sigmas: HOST arrays of m DEVICE pointers (n elements each);
+ * 1 <= m <= SPECTRE_PERM_MAX_COLS. delta0 = delta^(index of the chunk's first
+ * column), the value halo2 carries from chunk to chunk; NULL: one.
+ * d_num, d_den: n elements each. They must not overlap each other or any
+ * input. Exactly n elements of each are written; inputs are never written.
+ * n is any row count <= 2^28 (the caller passes the usable rows or the
+ * whole column). n == 0: nothing is done. */
+int spectre_gpu_fr_permutation_terms(spectre_gpu_ctx*, int dev,
+        const void* const* d_values, const void* const* d_sigmas, uint32_t m,
+        const uint8_t beta[32], const uint8_t gamma[32],
+        const uint8_t omega[32], const uint8_t delta0[32],
+        const uint8_t delta[32], void* d_num, void* d_den, uint64_t n);
 
 /* ---- device memory helpers (for C callers and the bench harness) ------- */
 int spectre_gpu_malloc(spectre_gpu_ctx*, int dev, size_t bytes, void** d_ptr);

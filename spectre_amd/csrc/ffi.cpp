@@ -739,6 +739,96 @@ int spectre_gpu_fr_lookup_permute(spectre_gpu_ctx* ctx, int dev,
                                     (fp256*)d_table_perm, u);
 }
 
+// ---------------------------------------------------------------- permutation argument
+int spectre_gpu_fr_powers(spectre_gpu_ctx* ctx, int dev, const uint8_t c[32],
+                          const uint8_t g[32], void* d_out, uint64_t n) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!g) {
+        set_err("fr_powers: null g");
+        return -3;
+    }
+    if (n > (1ull << 28)) {
+        set_err("fr_powers: n %llu > 2^28", (unsigned long long)n);
+        return -3;
+    }
+    if (n == 0) return 0;
+    if (!d_out) {
+        set_err("fr_powers: null device pointer d_out");
+        return -3;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 cv, gv;
+    if (c) ff_from_bytes(cv, c);
+    else ff_set_one<Fr>(cv);
+    ff_from_bytes(gv, g);
+    return fr_powers_device(ctx, dev, cv, gv, (fp256*)d_out, n);
+}
+
+int spectre_gpu_fr_permutation_terms(
+    spectre_gpu_ctx* ctx, int dev, const void* const* d_values,
+    const void* const* d_sigmas, uint32_t m, const uint8_t beta[32],
+    const uint8_t gamma[32], const uint8_t omega[32], const uint8_t delta0[32],
+    const uint8_t delta[32], void* d_num, void* d_den, uint64_t n) {
+    if (check_dev(ctx, dev)) return -1;
+    if (m < 1 || m > SPECTRE_PERM_MAX_COLS) {
+        set_err("fr_permutation_terms: m %u outside [1, %u]", m,
+                SPECTRE_PERM_MAX_COLS);
+        return -3;
+    }
+    if (n > (1ull << 28)) {
+        set_err("fr_permutation_terms: n %llu > 2^28", (unsigned long long)n);
+        return -3;
+    }
+    if (!d_values || !d_sigmas || !beta || !gamma || !omega || !delta) {
+        set_err("fr_permutation_terms: null %s",
+                d_values && d_sigmas ? "beta/gamma/omega/delta"
+                                     : "column pointer array");
+        return -3;
+    }
+    if (n == 0) return 0;
+    if (!d_num || !d_den) {
+        set_err("fr_permutation_terms: null device pointer %s",
+                d_num ? "d_den" : "d_num");
+        return -3;
+    }
+    // the outputs lie clear of each other and of every input
+    const uintptr_t out[2] = {(uintptr_t)d_num, (uintptr_t)d_den};
+    if (out[0] < out[1] + 32 * n && out[1] < out[0] + 32 * n) {
+        set_err("fr_permutation_terms: d_num and d_den overlap");
+        return -3;
+    }
+    for (uint32_t j = 0; j < m; j++) {
+        const uintptr_t in[2] = {(uintptr_t)d_values[j],
+                                 (uintptr_t)d_sigmas[j]};
+        for (int k = 0; k < 2; k++) {
+            if (!in[k]) {
+                set_err("fr_permutation_terms: null device pointer %s[%u]",
+                        k ? "d_sigmas" : "d_values", j);
+                return -3;
+            }
+            for (int o = 0; o < 2; o++) {
+                if (in[k] < out[o] + 32 * n && out[o] < in[k] + 32 * n) {
+                    set_err("fr_permutation_terms: %s overlaps %s[%u]",
+                            o ? "d_den" : "d_num",
+                            k ? "d_sigmas" : "d_values", j);
+                    return -3;
+                }
+            }
+        }
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 b, g, w, d0, d;
+    ff_from_bytes(b, beta);
+    ff_from_bytes(g, gamma);
+    ff_from_bytes(w, omega);
+    if (delta0) ff_from_bytes(d0, delta0);
+    else ff_set_one<Fr>(d0);
+    ff_from_bytes(d, delta);
+    return fr_permutation_terms_device(
+        ctx, dev, (const fp256* const*)d_values, (const fp256* const*)d_sigmas,
+        m, b, g, w, d0, d, (fp256*)d_num, (fp256*)d_den, n);
+}
+
 // ---------------------------------------------------------------- memory
 int spectre_gpu_malloc(spectre_gpu_ctx* ctx, int dev, size_t bytes,
                        void** d_ptr) {

@@ -184,6 +184,8 @@ struct DeviceState {
     DevBuf<uint8_t> d_lk_tmp;    // hipCUB sort / scan temp storage (bytes)
     DevBuf<uint32_t> d_lk_words; // OR of the canonical limbs, miss count
     PinnedBuf<uint32_t> h_lk_words;  // their pinned landing spot
+    // ---- row-power tables of one perm.hip call: T1 (4096) || T2 ----
+    DevBuf<fp256> d_perm_pow;
     std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n
     // frees everything this device owns; the caller has made it current
     void release() {
@@ -191,7 +193,7 @@ struct DeviceState {
         release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
                     d_ntt_io, d_cosetA, d_gate, d_gp_prods, h_gp_last,
                     d_poly_parts, h_poly_out, d_lk_canon, d_lk_ss, d_lk_keys,
-                    d_lk_idx, d_lk_tmp, d_lk_words, h_lk_words);
+                    d_lk_idx, d_lk_tmp, d_lk_words, h_lk_words, d_perm_pow);
         for (auto& kv : bases_cache) kv.second.release();
         bases_cache.clear();
         for (auto& kv : plans) kv.second.release();
@@ -318,3 +320,21 @@ int fr_lookup_permute_device(spectre_gpu_ctx* ctx, int dev,
                              const fp256* d_input, const fp256* d_table,
                              fp256* d_input_perm, fp256* d_table_perm,
                              uint64_t u);
+
+// perm.hip — out[i] = c * g^i for i < n <= 2^28, any field elements c and g
+// (synchronizes).
+int fr_powers_device(spectre_gpu_ctx* ctx, int dev, const fp256& c,
+                     const fp256& g, fp256* d_out, uint64_t n);
+// perm.hip — one chunk of the permutation argument's grand-product terms over
+// rows 0..n, n <= 2^28 (synchronizes):
+//   den[i] = prod_{j<m} (values[j][i] + beta*sigmas[j][i] + gamma)
+//   num[i] = prod_{j<m} (values[j][i] + beta*delta0*delta^j*omega^i + gamma)
+// d_values / d_sigmas = host arrays of m device pointers, 1 <= m <=
+// SPECTRE_PERM_MAX_COLS. The outputs overlap nothing.
+int fr_permutation_terms_device(spectre_gpu_ctx* ctx, int dev,
+                                const fp256* const* d_values,
+                                const fp256* const* d_sigmas, uint32_t m,
+                                const fp256& beta, const fp256& gamma,
+                                const fp256& omega, const fp256& delta0,
+                                const fp256& delta, fp256* d_num, fp256* d_den,
+                                uint64_t n);

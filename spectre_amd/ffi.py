@@ -179,6 +179,16 @@ def load_library() -> ctypes.CDLL:
         c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
         c.c_uint64,
     ]
+    lib.spectre_gpu_fr_powers.restype = c.c_int
+    lib.spectre_gpu_fr_powers.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
+    ]
+    lib.spectre_gpu_fr_permutation_terms.restype = c.c_int
+    lib.spectre_gpu_fr_permutation_terms.argtypes = [
+        c.c_void_p, c.c_int, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p),
+        c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
+    ]
     lib.spectre_gpu_malloc.restype = c.c_int
     lib.spectre_gpu_malloc.argtypes = [c.c_void_p, c.c_int, c.c_size_t,
                                        c.POINTER(c.c_void_p)]
@@ -595,6 +605,43 @@ class SpectreGpu:
             self._ctx, dev, ctypes.c_void_p(d_input), ctypes.c_void_p(d_table),
             ctypes.c_void_p(d_input_perm), ctypes.c_void_p(d_table_perm), u)
         self._check(rc, "fr_lookup_permute")
+
+    PERM_MAX_COLS = 8  # = SPECTRE_PERM_MAX_COLS
+
+    def fr_powers(self, c: bytes | None, g: bytes, d_out: int, n: int,
+                  dev: int = 0) -> None:
+        """d_out[i] = c * g^i for i < n (c None: one) over Montgomery Fr; c
+        and g are any field elements. With c = zeta and g = omega_ext this is
+        the X column of the extended-domain permutation constraint."""
+        cc = (ctypes.c_uint8 * 32).from_buffer_copy(c) if c else None
+        gg = (ctypes.c_uint8 * 32).from_buffer_copy(g)
+        rc = self._lib.spectre_gpu_fr_powers(
+            self._ctx, dev, cc, gg, ctypes.c_void_p(d_out) if d_out else None,
+            n)
+        self._check(rc, "fr_powers")
+
+    def fr_permutation_terms(self, d_values: list[int], d_sigmas: list[int],
+                             beta: bytes, gamma: bytes, omega: bytes,
+                             delta0: bytes | None, delta: bytes, d_num: int,
+                             d_den: int, n: int, dev: int = 0) -> None:
+        """One chunk of halo2's permutation::prover::commit over rows 0..n of
+        m = len(d_values) columns (1..PERM_MAX_COLS):
+          d_den[i] = prod_j (values[j][i] + beta*sigmas[j][i] + gamma)
+          d_num[i] = prod_j (values[j][i] + beta*delta0*delta^j*omega^i + gamma)
+        delta0 None: one. fr_grand_product(d_num, d_den, z0) then gives the
+        chunk's Z column. The outputs must overlap nothing."""
+        assert len(d_values) == len(d_sigmas)
+        m = len(d_values)
+        vals = (ctypes.c_void_p * max(1, m))(*d_values)
+        sigs = (ctypes.c_void_p * max(1, m))(*d_sigmas)
+        b, gm, w, d = ((ctypes.c_uint8 * 32).from_buffer_copy(x)
+                       for x in (beta, gamma, omega, delta))
+        d0 = (ctypes.c_uint8 * 32).from_buffer_copy(delta0) if delta0 else None
+        rc = self._lib.spectre_gpu_fr_permutation_terms(
+            self._ctx, dev, vals, sigs, m, b, gm, w, d0, d,
+            ctypes.c_void_p(d_num) if d_num else None,
+            ctypes.c_void_p(d_den) if d_den else None, n)
+        self._check(rc, "fr_permutation_terms")
 
     # ---- device memory helpers ----
     def malloc(self, nbytes: int, dev: int = 0) -> int:
