@@ -4,6 +4,7 @@
 #include "spectre_gpu.h"
 #include "ff.hpp"
 #include "g1.hpp"
+#include "powtab.hpp"
 #include <array>
 #include <map>
 #include <mutex>
@@ -96,8 +97,8 @@ struct NttPlan {
     uint32_t npass = 0;      // axes of the split, one global pass each
     uint32_t k[3] = {};      // log2 axis sizes; the last is the contiguous one
     DevBuf<fp256> tw[3];     // butterfly twiddles per axis, 2^(k-1) entries
-    DevBuf<fp256> twB;  // T1 || T2 omega-power lookup (w^e = T1[e&fff]*T2[e>>12])
-    uint32_t t1n = 0;        // entries of T1
+    DevBuf<fp256> twB;       // the omega-power table (powtab.hpp), e < n
+    PowTable omega = {};     // its two halves
     void release() { release_all(tw[0], tw[1], tw[2], twB); }
 };
 
@@ -162,7 +163,10 @@ struct DeviceState {
     DevBuf<fp256> d_ntt_io;   // cached device buffer for host-pointer NTTs
                               // (the Rust seam calls this path ~40-60x per
                               // proof; no per-call hipMalloc)
-    DevBuf<fp256> d_cosetA;   // coset power tables T1 || T2
+    // The power table (powtab.hpp) of the call in flight: an NTT's coset
+    // table or a perm.hip call's row powers. Every user holds ctx->mu and
+    // synchronizes the stream before it returns, and no call uses both.
+    DevBuf<fp256> d_pow;
     // ---- gate-eval scratch (column pointers, constants, program; bytes) ----
     DevBuf<uint8_t> d_gate;
     // ---- grand-product scratch: tile products -> prefixes (+ the grand
@@ -184,16 +188,14 @@ struct DeviceState {
     DevBuf<uint8_t> d_lk_tmp;    // hipCUB sort / scan temp storage (bytes)
     DevBuf<uint32_t> d_lk_words; // OR of the canonical limbs, miss count
     PinnedBuf<uint32_t> h_lk_words;  // their pinned landing spot
-    // ---- row-power tables of one perm.hip call: T1 (4096) || T2 ----
-    DevBuf<fp256> d_perm_pow;
     std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n
     // frees everything this device owns; the caller has made it current
     void release() {
         for (auto& sl : slots) sl.release(stream);
         release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
-                    d_ntt_io, d_cosetA, d_gate, d_gp_prods, h_gp_last,
+                    d_ntt_io, d_pow, d_gate, d_gp_prods, h_gp_last,
                     d_poly_parts, h_poly_out, d_lk_canon, d_lk_ss, d_lk_keys,
-                    d_lk_idx, d_lk_tmp, d_lk_words, h_lk_words, d_perm_pow);
+                    d_lk_idx, d_lk_tmp, d_lk_words, h_lk_words);
         for (auto& kv : bases_cache) kv.second.release();
         bases_cache.clear();
         for (auto& kv : plans) kv.second.release();

@@ -32,9 +32,9 @@
 // m = tA*B + tB) stores to out[tA + A*tB + AB*t]. In general the twiddle
 // after a pass is w^((t << sum of the earlier axes' k) * (m & (S-1))). Two
 // axes are the case B = 1, one axis A = B = 1. All exponents < n <= 2^28.
-// Twiddle/coset powers g^e resolve via two tables, 4096 and n/4096 entries:
-//   g^e = T1[e & 0xfff] * T2[e >> 12]   (one mul + two cached loads)
-// the omega ones built once per (omega, log_n) plan and cached on device.
+// Twiddle/coset powers g^e resolve via the two-level table of powtab.hpp (one
+// mul + two cached loads), the omega one built once per (omega, log_n) plan
+// and cached on device, the coset one per call.
 //
 // The extend transform (halo2's coeff_to_extended: 2^k coefficients, zeros up
 // to 2^(k+e), coset NTT there) is the same plan and pass loop at 2^(k+e) with
@@ -58,11 +58,8 @@ using NttFr = Fr;          // block geometries
 using NttFr = FrCios;
 #endif
 
-#define THREADS 256       // pow-table builder
 #define NTT_THREADS 1024  // NTT passes: 16 waves/block so one LDS-resident
                           // block still puts 4 waves on every SIMD
-#define TW_LOW_BITS 12
-#define TW_LOW_MASK 0xfffu
 
 __device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t bits) {
     return bits ? (__brev(x) >> (32 - bits)) : 0;
@@ -74,21 +71,6 @@ __device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t bits) {
 // separate regions (lo at [i], hi at [H+i]; lds_split_ld / lds_split_st):
 // consecutive elements stride 4 banks and one lane group covers all 64 banks.
 #define LDS_BYTES(L) ((uint32_t)(L) * 32u)
-// g^e via the 2D power table (e < n)
-__device__ __forceinline__ void tw_lookup(fp256& o, const fp256* T1,
-                                          const fp256* T2, uint32_t e) {
-    ff_mul<NttFr>(o, T1[e & TW_LOW_MASK], T2[e >> TW_LOW_BITS]);
-}
-
-// out[j] = base^j, j < count
-__global__ void k_pow_table(fp256 base, fp256* __restrict__ out,
-                            uint32_t count) {
-    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= count) return;
-    fp256 v;
-    ff_pow_u32<NttFr>(v, base, j);
-    out[j] = v;
-}
 
 // in-LDS DIF butterflies over L = 2^logL elements; twL[j] = (root)^j, j < L/2.
 // On exit lds[s] holds DFT output index bitrev(s, logL).
@@ -177,10 +159,10 @@ struct NttPass {
     const fp256* in;
     fp256* out;
     const fp256* twL;        // (axis root)^j, j < L/2
-    const fp256 *T1, *T2;    // omega power tables (passes before the last)
-    const fp256 *cT1, *cT2;  // coset power tables; null = no coset multiply
-                             // in this pass (forward: on load, inverse: on
-                             // the last pass's store)
+    PowTable omega;          // omega powers (passes before the last)
+    PowTable coset;          // coset powers; null T1 = no coset multiply in
+                             // this pass (forward: on load, inverse: on the
+                             // last pass's store)
     fp256 scale;             // n^{-1}, applied by the last pass of an inverse
     uint32_t logL, logS;
     uint32_t tw_shift;       // sum of the earlier axes' log sizes
@@ -231,9 +213,9 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(
             ff_set_zero(v);
             if (pos < n_in) {
                 v = p.in[pos];
-                if (p.cT1) {  // forward coset: g^(original index)
+                if (p.coset.T1) {  // forward coset: g^(original index)
                     fp256 f;
-                    tw_lookup(f, p.cT1, p.cT2, (uint32_t)pos);
+                    pow_lookup<NttFr>(f, p.coset, (uint32_t)pos);
                     ff_mul<NttFr>(v, v, f);
                 }
             }
@@ -250,9 +232,9 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(
         for (uint32_t s = threadIdx.x; s < L; s += blockDim.x) {
             const uint64_t pos = base + ((uint64_t)s << p.logS);
             fp256 v = p.in[pos];
-            if (p.cT1 && !p.inverse) {  // forward coset: g^(original index)
+            if (p.coset.T1 && !p.inverse) {  // forward coset: g^(input index)
                 fp256 f;
-                tw_lookup(f, p.cT1, p.cT2, (uint32_t)pos);
+                pow_lookup<NttFr>(f, p.coset, (uint32_t)pos);
                 ff_mul<NttFr>(v, v, f);
             }
             lds_split_st(lds4, s, H, v);
@@ -266,7 +248,7 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(
         lds_split_ld(lds4, s, H, v);
         uint64_t opos;
         if (!p.last) {
-            tw_lookup(f, p.T1, p.T2, (t << p.tw_shift) * mS);
+            pow_lookup<NttFr>(f, p.omega, (t << p.tw_shift) * mS);
             ff_mul<NttFr>(v, v, f);
             opos = base + ((uint64_t)t << p.logS);
         } else {
@@ -275,8 +257,8 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(
             const uint32_t tB = m & ((1u << p.fin_logB) - 1);
             opos = (uint64_t)tA + ((uint64_t)tB << p.fin_logA) +
                    ((uint64_t)t << (p.fin_logA + p.fin_logB));
-            if (p.cT1 && p.inverse) {  // inverse coset: g^(output index)
-                tw_lookup(f, p.cT1, p.cT2, (uint32_t)opos);
+            if (p.coset.T1 && p.inverse) {  // inverse coset: g^(output index)
+                pow_lookup<NttFr>(f, p.coset, (uint32_t)opos);
                 ff_mul<NttFr>(v, v, f);
             }
         }
@@ -321,36 +303,17 @@ uint32_t ntt_split(uint32_t log_n, bool force3, uint32_t k[3]) {
     return 2;
 }
 
-static void build_table(DeviceState& ds, const fp256& base, fp256* out,
-                        uint32_t count) {
-    hipLaunchKernelGGL(k_pow_table, dim3((count + THREADS - 1) / THREADS),
-                       dim3(THREADS), 0, ds.stream, base, out, count);
-}
-
-// the tw_lookup tables of g for exponents < n: T1 (t1n entries) || T2
-static int build_lookup_tables(DeviceState& ds, const fp256& g, uint32_t n,
-                               uint32_t t1n, DevBuf<fp256>& buf) {
-    const uint32_t t2n = n / t1n;
-    RC_TRY(buf.reserve((size_t)t1n + t2n));
-    fp256 gT2;
-    ff_pow_u32<NttFr>(gT2, g, 1u << TW_LOW_BITS);
-    build_table(ds, g, buf.ptr, t1n);
-    build_table(ds, gT2, buf.ptr + t1n, t2n);
-    return 0;
-}
-
 // choose the split and build the twiddle tables for (omega, log_n) into p
 static int build_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
                       bool force3, NttPlan& p) {
     p.npass = ntt_split(log_n, force3, p.k);
-    p.t1n = 1u << (log_n < TW_LOW_BITS ? log_n : TW_LOW_BITS);
-    RC_TRY(build_lookup_tables(ds, omega, 1u << log_n, p.t1n, p.twB));
+    RC_TRY(pow_tables_build(ds, omega, nullptr, 1u << log_n, p.twB, &p.omega));
     for (uint32_t i = 0; i < p.npass; i++) {
         fp256 root;  // of axis i's DFT
         ff_pow_u32<NttFr>(root, omega, 1u << (log_n - p.k[i]));
         const uint32_t half = 1u << (p.k[i] - 1);
         RC_TRY(p.tw[i].reserve(half));
-        build_table(ds, root, p.tw[i].ptr, half);
+        pow_linear_build(ds, root, p.tw[i].ptr, half);
     }
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
@@ -418,11 +381,11 @@ static int ntt_run(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
     RC_TRY(get_plan(ds, omega, log_n, ctx->ntt_force3, &plan));
     RC_TRY(ds.d_ntt_tmp.reserve(n));
     fp256* const tmp = ds.d_ntt_tmp.ptr;
-    if (coset_gen)  // coset power tables (per call; tiny)
-        RC_TRY(build_lookup_tables(ds, *coset_gen, n, plan->t1n, ds.d_cosetA));
+    PowTable ctab{};
+    if (coset_gen)  // coset power table (per call; tiny)
+        RC_TRY(pow_tables_build(ds, *coset_gen, nullptr, n, ds.d_pow, &ctab));
     NttPass pass{};
-    pass.T1 = plan->twB.ptr;
-    pass.T2 = plan->twB.ptr + plan->t1n;
+    pass.omega = plan->omega;
     pass.inverse = inverse ? 1 : 0;
     if (inverse) {  // n^{-1}
         fp256 ncanon, nm;
@@ -447,8 +410,7 @@ static int ntt_run(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
             pass.fin_logA = done - pass.fin_logB;
         }
         const bool coset = coset_gen && (inverse ? last : first);
-        pass.cT1 = coset ? ds.d_cosetA.ptr : nullptr;
-        pass.cT2 = coset ? ds.d_cosetA.ptr + plan->t1n : nullptr;
+        pass.coset = coset ? ctab : PowTable{};
         launch_pass(ds.stream, pass, log_n, first ? ext_bits : -1);
         done += plan->k[i];
     }

@@ -7,14 +7,12 @@
 // (zeta, omega_ext) is the X of the extended-domain permutation constraint, an
 // ordinary gate_eval column.
 //
-// Row powers come from the two-level table ntt.hip uses for its twiddles,
-//   g^i = T1[i & 0xfff] * T2[i >> 12],
-// built per call on the stream (4096 + ceil(n / 4096) entries, 0.4% of the
-// rows at 2^20, in one launch) for ANY field element g: an NTT plan's cached
-// tables exist only for roots of unity and only for exponents below that
-// plan's n, so they are not looked at here. fr_powers
-// folds c into T2 and spends one multiply per row; the terms kernel spends
-// one multiply on omega^i and shares it among the m columns.
+// Row powers g^i come from the two-level table of powtab.hpp, built per call
+// on the stream (4096 + ceil(n / 4096) entries, 0.4% of the rows at 2^20, in
+// one launch) for ANY field element g: an NTT plan's cached table exists only
+// for roots of unity and only for exponents below that plan's n, so it is not
+// looked at here. fr_powers folds c into T2: one multiply per row; the terms
+// kernel spends one multiply on omega^i and shares it among the m columns.
 //
 // Both kernels put row i in lane i: every column access is the two 16-byte
 // loads per element of k_fr_gate_eval, no LDS, no scratch. They compute in
@@ -25,97 +23,14 @@
 using PermFr = FrCios;
 
 #define THREADS 256
-#define PW_LOW_BITS 12
-#define PW_LOW (1u << PW_LOW_BITS)
-#define PW_LOW_MASK (PW_LOW - 1u)
-
-// ---- the two power tables, one launch ---------------------------------------
-// A table entry g^e is a product of one constant per base-4 digit of e,
-// c[w][d - 1] = g^(d * 4^w): the host squares its way up the 14 windows (a
-// few dozen multiplies) and hands them over in the kernel arguments, so an
-// entry costs at most 6 (T1) or 8 (T2) dependent multiplies where a
-// square-and-multiply chain per entry costs up to 24 — the build is a
-// latency chain on a handful of waves, and its depth is its time. T1's
-// exponent j uses windows 0..5, T2's exponent 4096 j windows 6..13.
-#define PW_WINDOWS 14
-#define PW_LOW_WINDOWS (PW_LOW_BITS / 2)
-struct PowWindows {
-    fp256 c[PW_WINDOWS][3];
-};
-
-// Blocks [0, nb1): t1[j] = g^j, j < t1n. Blocks from nb1: t2[j] = scale *
-// g^(4096 j), j < t2n. nwin1 / nwin2 = base-4 digits of t1n - 1 / t2n - 1.
-__global__ __launch_bounds__(THREADS) void k_perm_pow_tables(
-    PowWindows pw, fp256 scale, fp256* __restrict__ t1, uint32_t t1n,
-    uint32_t nwin1, fp256* __restrict__ t2, uint32_t t2n, uint32_t nwin2,
-    uint32_t nb1) {
-    const bool high = blockIdx.x >= nb1;
-    const uint32_t j =
-        (blockIdx.x - (high ? nb1 : 0u)) * blockDim.x + threadIdx.x;
-    if (j >= (high ? t2n : t1n)) return;
-    const uint32_t w0 = high ? PW_LOW_WINDOWS : 0u;
-    const uint32_t nwin = high ? nwin2 : nwin1;
-    fp256 acc;
-    if (high) acc = scale;
-    else ff_set_one<PermFr>(acc);
-#pragma unroll 1
-    for (uint32_t w = 0; w < nwin; w++) {
-        const uint32_t d = (j >> (2 * w)) & 3u;
-        fp256 f, t;
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            f.l[i] = d == 1 ? pw.c[w0 + w][0].l[i]
-                            : (d == 2 ? pw.c[w0 + w][1].l[i]
-                                      : pw.c[w0 + w][2].l[i]);
-        ff_mul<PermFr>(t, acc, f);
-#pragma unroll
-        for (int i = 0; i < 8; i++) acc.l[i] = d ? t.l[i] : acc.l[i];
-    }
-    (high ? t2 : t1)[j] = acc;
-}
-
-static uint32_t base4_digits(uint32_t x) {
-    uint32_t d = 0;
-    for (; x; x >>= 2) d++;
-    return d;
-}
-
-// T1 (min(n, 4096) entries, g^j) || T2 (ceil(n / 4096) entries,
-// scale * g^(4096 j)) into ds.d_perm_pow; enqueued, not synchronized.
-static int build_power_tables(DeviceState& ds, const fp256& g,
-                              const fp256& scale, uint64_t n,
-                              const fp256** T1, const fp256** T2) {
-    const uint32_t t1n = n < PW_LOW ? (uint32_t)n : PW_LOW;
-    const uint32_t t2n = (uint32_t)((n + PW_LOW - 1) >> PW_LOW_BITS);
-    RC_TRY(ds.d_perm_pow.reserve((size_t)PW_LOW + t2n));
-    PowWindows pw;
-    fp256 b = g;
-    for (int w = 0; w < PW_WINDOWS; w++) {
-        pw.c[w][0] = b;
-        ff_sqr<PermFr>(pw.c[w][1], b);
-        ff_mul<PermFr>(pw.c[w][2], pw.c[w][1], b);
-        ff_sqr<PermFr>(b, pw.c[w][1]);
-    }
-    fp256* const t1 = ds.d_perm_pow.ptr;
-    fp256* const t2 = t1 + PW_LOW;
-    const uint32_t nb1 = (t1n + THREADS - 1) / THREADS;
-    const uint32_t nb2 = (t2n + THREADS - 1) / THREADS;
-    hipLaunchKernelGGL(k_perm_pow_tables, dim3(nb1 + nb2), dim3(THREADS), 0,
-                       ds.stream, pw, scale, t1, t1n, base4_digits(t1n - 1),
-                       t2, t2n, base4_digits(t2n - 1), nb1);
-    *T1 = t1;
-    *T2 = t2;
-    return 0;
-}
 
 // ---- out[i] = c * g^i ------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void k_fr_powers(
-    const fp256* __restrict__ T1, const fp256* __restrict__ T2,
-    fp256* __restrict__ out, uint64_t n) {
+    PowTable tab, fp256* __restrict__ out, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     fp256 r;
-    ff_mul<PermFr>(r, T1[(uint32_t)i & PW_LOW_MASK], T2[i >> PW_LOW_BITS]);
+    pow_lookup<PermFr>(r, tab, i);
     out[i] = r;
 }
 
@@ -124,11 +39,11 @@ int fr_powers_device(spectre_gpu_ctx* ctx, int dev, const fp256& c,
     DeviceState& ds = ctx->devs[dev];
     HIP_TRY(hipSetDevice(ds.device_id));
     if (n == 0) return 0;
-    const fp256 *T1, *T2;
-    RC_TRY(build_power_tables(ds, g, c, n, &T1, &T2));
+    PowTable tab;
+    RC_TRY(pow_tables_build(ds, g, &c, n, ds.d_pow, &tab));
     hipLaunchKernelGGL(k_fr_powers,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
-                       dim3(THREADS), 0, ds.stream, T1, T2, d_out, n);
+                       dim3(THREADS), 0, ds.stream, tab, d_out, n);
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -160,13 +75,12 @@ __device__ __forceinline__ void perm_factors(const PermArgs& a, uint32_t j,
 // scalars), so both running products stay in registers; asking for it
 // unrolled per m changes neither the register count nor the scratch (none).
 __global__ __launch_bounds__(THREADS) void k_fr_perm_terms(
-    PermArgs a, uint32_t m, const fp256* __restrict__ T1,
-    const fp256* __restrict__ T2, fp256* __restrict__ num,
+    PermArgs a, uint32_t m, PowTable tab, fp256* __restrict__ num,
     fp256* __restrict__ den, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     fp256 w;  // omega^i
-    ff_mul<PermFr>(w, T1[(uint32_t)i & PW_LOW_MASK], T2[i >> PW_LOW_BITS]);
+    pow_lookup<PermFr>(w, tab, i);
     fp256 pn, pd;
     perm_factors(a, 0, i, w, pn, pd);
 #pragma unroll 1
@@ -201,14 +115,11 @@ int fr_permutation_terms_device(spectre_gpu_ctx* ctx, int dev,
         a.bd[j] = bd;
         ff_mul<PermFr>(bd, bd, delta);
     }
-    fp256 one;
-    ff_set_one<PermFr>(one);
-    const fp256 *T1, *T2;
-    RC_TRY(build_power_tables(ds, omega, one, n, &T1, &T2));
+    PowTable tab;
+    RC_TRY(pow_tables_build(ds, omega, nullptr, n, ds.d_pow, &tab));
     hipLaunchKernelGGL(k_fr_perm_terms,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
-                       dim3(THREADS), 0, ds.stream, a, m, T1, T2, d_num, d_den,
-                       n);
+                       dim3(THREADS), 0, ds.stream, a, m, tab, d_num, d_den, n);
     HIP_TRY(hipStreamSynchronize(ds.stream));
     HIP_TRY(hipGetLastError());
     return 0;

@@ -306,6 +306,53 @@ def test_constraint_closes_on_the_device(dev, gpu):
     assert res[:32 * (n - 1)] == bytes(32 * (n - 1))
 
 
+# ------------------------------------------------- the shared power-table scratch
+def test_ntt_and_permutation_calls_share_one_table_buffer(oracle, columns):
+    """The coset table of an NTT and the row powers of fr_powers /
+    fr_permutation_terms are built into one per-device buffer. One context of
+    its own (the buffer starts empty), five calls in a row that grow it, reuse
+    it at a smaller n (below 4096, so the low table is short) and switch
+    between its users; every result byte-exact."""
+    from spectre_amd import SpectreGpu
+    rng = random.Random(0x5c7a)
+    data = oracle.gen_fr_vector(1 << 13, seed=0x5c7b)
+    g5, g5_inv = pr.enc(5), pr.enc(pow(5, -1, R))
+    d = Dev(SpectreGpu([0]))
+    try:
+        def coset_ntt(log_n, inverse):
+            src = data[:32 << log_n]
+            w = root(log_n)
+            w, g = (pow(w, -1, R), g5_inv) if inverse else (w, g5)
+            p = d.put(src)
+            d.g.ntt_device(p, log_n, pr.enc(w), inverse=inverse, coset_gen=g)
+            want = oracle.ntt(src, log_n, pr.enc(w), inverse=inverse,
+                              coset_gen=g)
+            assert d.get(p, 1 << log_n) == want, \
+                f"coset NTT 2^{log_n} inverse={inverse}"
+
+        coset_ntt(13, False)
+        n, c, g = 3 * T1 + 5, rng.randrange(1, R), rng.randrange(2, R)
+        assert gpu_powers(d, c, g, n) == pr.mont(pr.powers(c, g, n))
+        coset_ntt(10, False)
+        m, n, omega = 2, 257, root(9)
+        beta, gamma = columns["beta"], columns["gamma"]
+        values = [c[:n] for c in columns["values"][:m]]
+        sigmas = [c[:n] for c in columns["sigmas"][:m]]
+        d_in = [d.put(pr.mont(c)) for c in values + sigmas]
+        d_num, d_den = d.out(n), d.out(n)
+        d.g.fr_permutation_terms(
+            d_in[:m], d_in[m:], pr.enc(beta), pr.enc(gamma), pr.enc(omega),
+            None, pr.enc(DELTA), d_num, d_den, n)
+        want_num, want_den = pr.terms(values, sigmas, beta, gamma, omega, 1,
+                                      DELTA, n)
+        assert d.get_guarded(d_num, n, "d_num") == pr.mont(want_num)
+        assert d.get_guarded(d_den, n, "d_den") == pr.mont(want_den)
+        coset_ntt(13, True)
+    finally:
+        d.free()
+        d.g.close()
+
+
 # ------------------------------------------------------------ argument checks
 def test_argument_checks(dev, gpu, columns):
     n = 300

@@ -12,10 +12,11 @@ buffers, next to
   * the per-call build of the row-power tables. It has no entry point of its
     own, so it is measured as a difference: fr_powers over 4096 rows (the
     whole low table, 4096 chains of six multiplies, plus 16 workgroups of
-    output) minus fr_powers over 1 row (the same two launches and the
-    synchronize, two table entries). Every larger call builds that same low
-    table, and its n / 4096 high entries in further workgroups of the same
-    launch.
+    output) minus fr_powers over 1 row (the same two launches, the table
+    builder k_pow_tables and k_fr_powers, and the synchronize; two table
+    entries). Every larger call builds that same low table, and its n / 4096
+    high entries in further workgroups of the builder's one launch. The NTT's
+    per-call coset table is the same builder and the same launch.
 
 Every timed call ends in the library's stream synchronize, so a host clock
 around it is the call time. Warm-up calls come first (code-object load and
