@@ -189,6 +189,21 @@ static int check_dev(spectre_gpu_ctx* ctx, int dev) {
     return 0;
 }
 
+// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+static bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b,
+                           uint64_t b_bytes) {
+    return (uintptr_t)a < (uintptr_t)b + b_bytes &&
+           (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+
+// the element at `bytes`, or one where the caller passed NULL
+static fp256 fr_or_one(const uint8_t* bytes) {
+    fp256 v;
+    if (bytes) ff_from_bytes(v, bytes);
+    else ff_set_one<Fr>(v);
+    return v;
+}
+
 // Horner over the 16 windows + normalize to affine (host; <=256 point ops).
 static void winsums_to_affine(const g1_jac* wins, uint8_t out[64]) {
     g1_jac res;
@@ -517,9 +532,9 @@ int spectre_gpu_ntt_fr_extend_device(spectre_gpu_ctx* ctx, int dev,
         return -3;
     }
     // d_out is d_coeffs or lies clear of its n elements
-    const uintptr_t src = (uintptr_t)d_coeffs, dst = (uintptr_t)d_out;
-    if (src != dst && src < dst + (32ull << (log_n + ext_bits)) &&
-        dst < src + (32ull << log_n)) {
+    if (d_coeffs != d_out &&
+        ranges_overlap(d_coeffs, 32ull << log_n, d_out,
+                       32ull << (log_n + ext_bits))) {
         set_err("ntt_extend: d_out overlaps d_coeffs without being equal");
         return -1;
     }
@@ -634,12 +649,10 @@ int spectre_gpu_fr_grand_product(spectre_gpu_ctx* ctx, int dev,
         return -1;
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    fp256 seed, last;
-    if (z0) ff_from_bytes(seed, z0);
-    else ff_set_one<Fr>(seed);
+    fp256 last;
     RC_TRY(fr_grand_product_device(ctx, dev, (const fp256*)d_num,
-                                   (const fp256*)d_den, seed, (fp256*)d_z, n,
-                                   out_last ? &last : nullptr));
+                                   (const fp256*)d_den, fr_or_one(z0),
+                                   (fp256*)d_z, n, out_last ? &last : nullptr));
     if (out_last) ff_to_bytes(out_last, last);
     return 0;
 }
@@ -724,8 +737,7 @@ int spectre_gpu_fr_lookup_permute(spectre_gpu_ctx* ctx, int dev,
     }
     for (int i = 0; i < 4; i++) {
         for (int j = i + 1; j < 4; j++) {
-            const uintptr_t a = (uintptr_t)buf[i], b = (uintptr_t)buf[j];
-            if (a < b + 32 * u && b < a + 32 * u) {
+            if (ranges_overlap(buf[i], 32 * u, buf[j], 32 * u)) {
                 set_err("fr_lookup_permute: %s and %s overlap", name[i],
                         name[j]);
                 return -1;
@@ -757,11 +769,9 @@ int spectre_gpu_fr_powers(spectre_gpu_ctx* ctx, int dev, const uint8_t c[32],
         return -3;
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    fp256 cv, gv;
-    if (c) ff_from_bytes(cv, c);
-    else ff_set_one<Fr>(cv);
+    fp256 gv;
     ff_from_bytes(gv, g);
-    return fr_powers_device(ctx, dev, cv, gv, (fp256*)d_out, n);
+    return fr_powers_device(ctx, dev, fr_or_one(c), gv, (fp256*)d_out, n);
 }
 
 int spectre_gpu_fr_permutation_terms(
@@ -792,14 +802,13 @@ int spectre_gpu_fr_permutation_terms(
         return -3;
     }
     // the outputs lie clear of each other and of every input
-    const uintptr_t out[2] = {(uintptr_t)d_num, (uintptr_t)d_den};
-    if (out[0] < out[1] + 32 * n && out[1] < out[0] + 32 * n) {
+    const void* const out[2] = {d_num, d_den};
+    if (ranges_overlap(d_num, 32 * n, d_den, 32 * n)) {
         set_err("fr_permutation_terms: d_num and d_den overlap");
         return -3;
     }
     for (uint32_t j = 0; j < m; j++) {
-        const uintptr_t in[2] = {(uintptr_t)d_values[j],
-                                 (uintptr_t)d_sigmas[j]};
+        const void* const in[2] = {d_values[j], d_sigmas[j]};
         for (int k = 0; k < 2; k++) {
             if (!in[k]) {
                 set_err("fr_permutation_terms: null device pointer %s[%u]",
@@ -807,7 +816,7 @@ int spectre_gpu_fr_permutation_terms(
                 return -3;
             }
             for (int o = 0; o < 2; o++) {
-                if (in[k] < out[o] + 32 * n && out[o] < in[k] + 32 * n) {
+                if (ranges_overlap(in[k], 32 * n, out[o], 32 * n)) {
                     set_err("fr_permutation_terms: %s overlaps %s[%u]",
                             o ? "d_den" : "d_num",
                             k ? "d_sigmas" : "d_values", j);
@@ -817,16 +826,14 @@ int spectre_gpu_fr_permutation_terms(
         }
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    fp256 b, g, w, d0, d;
+    fp256 b, g, w, d;
     ff_from_bytes(b, beta);
     ff_from_bytes(g, gamma);
     ff_from_bytes(w, omega);
-    if (delta0) ff_from_bytes(d0, delta0);
-    else ff_set_one<Fr>(d0);
     ff_from_bytes(d, delta);
     return fr_permutation_terms_device(
         ctx, dev, (const fp256* const*)d_values, (const fp256* const*)d_sigmas,
-        m, b, g, w, d0, d, (fp256*)d_num, (fp256*)d_den, n);
+        m, b, g, w, fr_or_one(delta0), d, (fp256*)d_num, (fp256*)d_den, n);
 }
 
 // ---------------------------------------------------------------- memory

@@ -136,19 +136,21 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
         set_err("gate_eval: program leaves %d values on the stack (need 1)", depth);
         return -3;
     }
-    // device staging: [col ptrs][constants][program], one cached buffer
-    const size_t ptr_b = (size_t)ncols * sizeof(fp256*);
-    const size_t con_b = (size_t)nconst * sizeof(fp256);
-    const size_t prg_b = (size_t)nops * 12;
-    const size_t need = ptr_b + con_b + prg_b;
-    RC_TRY(ds.d_gate.reserve(need));
-    uint8_t* const d_gate = ds.d_gate.ptr;
-    HIP_TRY(hipMemcpyAsync(d_gate, cols, ptr_b, hipMemcpyHostToDevice,
-                           ds.stream));
-    if (con_b)
-        HIP_TRY(hipMemcpyAsync(d_gate + ptr_b, consts, con_b,
+    // device staging: [col ptrs][constants][program]
+    ScratchLayout lay;
+    const uint64_t o_ptr = lay.add<fp256*>(ncols);
+    const uint64_t o_con = lay.add<fp256>(nconst);
+    const uint64_t o_prg = lay.add<uint32_t>(3 * (uint64_t)nops);
+    RC_TRY(ds.d_call.reserve(lay.total));
+    const fp256** const d_cols = (const fp256**)(ds.d_call.ptr + o_ptr);
+    fp256* const d_consts = (fp256*)(ds.d_call.ptr + o_con);
+    uint32_t* const d_program = (uint32_t*)(ds.d_call.ptr + o_prg);
+    HIP_TRY(hipMemcpyAsync(d_cols, cols, ncols * sizeof(fp256*),
+                           hipMemcpyHostToDevice, ds.stream));
+    if (nconst)
+        HIP_TRY(hipMemcpyAsync(d_consts, consts, nconst * sizeof(fp256),
                                hipMemcpyHostToDevice, ds.stream));
-    HIP_TRY(hipMemcpyAsync(d_gate + ptr_b + con_b, program, prg_b,
+    HIP_TRY(hipMemcpyAsync(d_program, program, (size_t)nops * 12,
                            hipMemcpyHostToDevice, ds.stream));
     fp256 yv;
     ff_set_zero(yv);
@@ -158,13 +160,10 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
     hipLaunchKernelGGL(k_fr_gate_eval,
                        dim3((uint32_t)((n + GATE_THREADS - 1) / GATE_THREADS)),
                        dim3(GATE_THREADS), lds_bytes, ds.stream,
-                       (const fp256* const*)d_gate,
-                       (const fp256*)(d_gate + ptr_b),
-                       (const uint32_t*)(d_gate + ptr_b + con_b), nops, n,
+                       (const fp256* const*)d_cols, (const fp256*)d_consts,
+                       (const uint32_t*)d_program, nops, n,
                        rot_scale, y ? 1 : 0, yv, d_out);
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }
 
 // ---- pointwise Fr vector ops (quotient-phase gate-eval glue) --------------
@@ -200,9 +199,7 @@ int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
                        dim3(THREADS), 0, ds.stream, op, d_a, d_b, cv, d_out,
                        n);
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }
 
 // ---- out[i] = a[i] * table[i mod period] (divide_by_vanishing_poly) -------
@@ -233,7 +230,5 @@ int fr_vec_mul_periodic_device(spectre_gpu_ctx* ctx, int dev,
     hipLaunchKernelGGL(k_fr_vec_mul_periodic,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
                        dim3(THREADS), 0, ds.stream, d_a, tab, d_out, n);
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }

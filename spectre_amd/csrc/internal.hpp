@@ -93,6 +93,7 @@ void release_all(B&... b) {
     (b.release(), ...);
 }
 
+// Cached across calls, so a plan owns its tables (twB too: not in d_call).
 struct NttPlan {
     uint32_t npass = 0;      // axes of the split, one global pass each
     uint32_t k[3] = {};      // log2 axis sizes; the last is the contiguous one
@@ -149,53 +150,40 @@ struct DeviceState {
     int next_slot = 0;  // round-robin for the async API
     int num_cus = 0;              // filled with acc_resident_blocks
     int acc_resident_blocks = 0;  // k_bucket_acc blocks resident per CU
+    // ---- caller data held across a nested device call (a host-pointer
+    // entry point uploads, then calls the device one, which carves up
+    // d_call), so not part of d_call ----
     DevBuf<uint8_t> d_scalars;   // host-pointer MSM scratch (bytes)
     DevBuf<g1_affine> d_bases;   // uncached host-pointer bases (points)
     // key = (bases_id, n, shard layout): layout is num_gpus for the sharded
     // path (this device's contiguous chunk of an n-point set split num_gpus
     // ways) and 1 for the full set (batch path == num_gpus=1 shard).
     std::map<std::array<uint64_t, 3>, DevBuf<g1_affine>> bases_cache;
-    // ---- pinned staging for host-pointer uploads/downloads ----
-    PinnedBuf<uint8_t> h_stage[2];
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    // ---- NTT scratch (elements) ----
-    DevBuf<fp256> d_ntt_tmp;
     DevBuf<fp256> d_ntt_io;   // cached device buffer for host-pointer NTTs
                               // (the Rust seam calls this path ~40-60x per
                               // proof; no per-call hipMalloc)
-    // The power table (powtab.hpp) of the call in flight: an NTT's coset
-    // table or a perm.hip call's row powers. Every user holds ctx->mu and
-    // synchronizes the stream before it returns, and no call uses both.
-    DevBuf<fp256> d_pow;
-    // ---- gate-eval scratch (column pointers, constants, program; bytes) ----
-    DevBuf<uint8_t> d_gate;
-    // ---- grand-product scratch: tile products -> prefixes (+ the grand
-    // total in the last slot), and the pinned landing spot of that total ----
-    DevBuf<fp256> d_gp_prods;
-    PinnedBuf<fp256> h_gp_last;
-    // ---- opening-phase scratch: every level of tile partials of one
-    // evaluation / division (per point), and the pinned landing spot of the
-    // evaluations / the remainder ----
-    DevBuf<fp256> d_poly_parts;
-    PinnedBuf<fp256> h_poly_out;
-    // ---- lookup-permutation scratch (lookup.hip), u rows per call ----
-    DevBuf<fp256> d_lk_canon;    // 2u: canonical input | canonical table;
-                                 // the first half then takes canonical Ss
-    DevBuf<fp256> d_lk_ss;       // u: the sorted table, Montgomery
-    DevBuf<uint64_t> d_lk_keys;  // 2u: one limb's sort keys, in | out
-    DevBuf<uint32_t> d_lk_idx;   // 7u: two permutations, the flags !first
-                                 // and free, their ranks, repeated rows
-    DevBuf<uint8_t> d_lk_tmp;    // hipCUB sort / scan temp storage (bytes)
-    DevBuf<uint32_t> d_lk_words; // OR of the canonical limbs, miss count
-    PinnedBuf<uint32_t> h_lk_words;  // their pinned landing spot
+    // ---- pinned staging for host-pointer uploads/downloads ----
+    PinnedBuf<uint8_t> h_stage[2];
+    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    // ---- the call arena: all device scratch of the synchronous Fr calls
+    // (ntt, gate, poly, lookup, perm .hip), laid out per call with a
+    // ScratchLayout (scratch.hpp). Every user holds ctx->mu; reserves its
+    // whole call ONCE, before its first launch (growth frees the buffer: a
+    // second reserve would pull it out from under pointers kernels already
+    // hold); synchronizes the stream before it returns (call_finish); and
+    // keeps no pointer into it across calls. So no two users are live at
+    // once and the device holds the largest call's need, not the sum. The
+    // MSM slots are asynchronous and outlive the call: not in it. ----
+    DevBuf<uint8_t> d_call;
+    // pinned landing spot of a call's readback (call_finish), reserved on
+    // first use
+    PinnedBuf<uint8_t> h_call;
     std::map<std::array<uint8_t, 40>, NttPlan> plans;  // omega||log_n
     // frees everything this device owns; the caller has made it current
     void release() {
         for (auto& sl : slots) sl.release(stream);
-        release_all(d_scalars, d_bases, h_stage[0], h_stage[1], d_ntt_tmp,
-                    d_ntt_io, d_pow, d_gate, d_gp_prods, h_gp_last,
-                    d_poly_parts, h_poly_out, d_lk_canon, d_lk_ss, d_lk_keys,
-                    d_lk_idx, d_lk_tmp, d_lk_words, h_lk_words);
+        release_all(d_scalars, d_bases, d_ntt_io, h_stage[0], h_stage[1],
+                    d_call, h_call);
         for (auto& kv : bases_cache) kv.second.release();
         bases_cache.clear();
         for (auto& kv : plans) kv.second.release();
@@ -208,6 +196,23 @@ struct DeviceState {
         stream = nullptr;
     }
 };
+
+// The one epilogue of a synchronous device call: if dst is given, enqueue
+// the readback of bytes <= CALL_PINNED_BYTES from d_src into h_call; then
+// synchronize the stream, surface a launch error, and copy the bytes out.
+#define CALL_PINNED_BYTES 256  // eight fp256
+inline int call_finish(DeviceState& ds, void* dst = nullptr,
+                       const void* d_src = nullptr, size_t bytes = 0) {
+    if (dst) {
+        RC_TRY(ds.h_call.reserve(CALL_PINNED_BYTES));
+        HIP_TRY(hipMemcpyAsync(ds.h_call.ptr, d_src, bytes,
+                               hipMemcpyDeviceToHost, ds.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ds.stream));
+    HIP_TRY(hipGetLastError());
+    if (dst) memcpy(dst, ds.h_call.ptr, bytes);
+    return 0;
+}
 
 struct spectre_gpu_ctx {
     std::vector<DeviceState> devs;

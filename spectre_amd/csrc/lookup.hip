@@ -231,34 +231,55 @@ static uint32_t lk_blocks(uint32_t n) {
     return (n + LK_THREADS - 1) / LK_THREADS;
 }
 
-// Scratch of one call over u rows. d_lk_idx holds seven u-word arrays:
-// two permutations, notfirst, free, their two ranks, and rep.
-static int lk_reserve(DeviceState& ds, uint32_t u) {
-    RC_TRY(ds.d_lk_canon.reserve(2 * (size_t)u));
-    RC_TRY(ds.d_lk_ss.reserve(u));
-    RC_TRY(ds.d_lk_keys.reserve(2 * (size_t)u));
-    RC_TRY(ds.d_lk_idx.reserve(7 * (size_t)u));
-    RC_TRY(ds.d_lk_words.reserve(LK_WORDS));
-    RC_TRY(ds.h_lk_words.reserve(LK_WORDS));
+// Scratch of one call over u rows, carved out of the call arena.
+struct LkScratch {
+    fp256* canon;     // 2u: canonical input (later canonical Ss) | table
+    fp256* ss;        // u: the sorted table, Montgomery
+    uint64_t* keys;   // 2u: one limb's sort keys, in | out
+    uint32_t* idx;    // 7u: 2 permutations, !first, free, their ranks, rep
+    uint32_t* words;  // LK_WORDS: OR of the canonical limbs, miss count
+    uint8_t* tmp;     // hipCUB sort / scan temp storage
+    size_t tmp_bytes;
+};
+
+// The temp sizes come from null typed pointers: rocPRIM returns the size
+// before it looks at a key or value pointer.
+static int lk_reserve(DeviceState& ds, uint32_t u, LkScratch& s) {
     size_t sort_need = 0, scan_need = 0;
-    uint64_t* k = ds.d_lk_keys.ptr;
-    uint32_t* x = ds.d_lk_idx.ptr;
-    CUB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_need, k, k + u, x,
-                                               x + u, (int64_t)u, 0, 64,
-                                               ds.stream));
-    CUB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_need, x, x + u,
-                                             (int)u, ds.stream));
-    return ds.d_lk_tmp.reserve(sort_need > scan_need ? sort_need : scan_need);
+    uint64_t* const k = nullptr;
+    uint32_t* const x = nullptr;
+    CUB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_need, k, k, x, x,
+                                               (int64_t)u, 0, 64, ds.stream));
+    CUB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_need, x, x, (int)u,
+                                             ds.stream));
+    s.tmp_bytes = sort_need > scan_need ? sort_need : scan_need;
+    ScratchLayout lay;
+    const uint64_t o_canon = lay.add<fp256>(2 * (uint64_t)u);
+    const uint64_t o_ss = lay.add<fp256>(u);
+    const uint64_t o_keys = lay.add<uint64_t>(2 * (uint64_t)u);
+    const uint64_t o_idx = lay.add<uint32_t>(7 * (uint64_t)u);
+    const uint64_t o_words = lay.add<uint32_t>(LK_WORDS);
+    const uint64_t o_tmp = lay.add<uint8_t>(s.tmp_bytes);
+    RC_TRY(ds.d_call.reserve(lay.total));
+    uint8_t* const a = ds.d_call.ptr;
+    s.canon = (fp256*)(a + o_canon);
+    s.ss = (fp256*)(a + o_ss);
+    s.keys = (uint64_t*)(a + o_keys);
+    s.idx = (uint32_t*)(a + o_idx);
+    s.words = (uint32_t*)(a + o_words);
+    s.tmp = a + o_tmp;
+    return 0;
 }
 
 // LSD radix sort of one column's canonical values over the 64-bit limbs with
 // end_bit[l] > 0; *perm_out = the sorted order (one of the two permutation
-// arrays at the front of d_lk_idx).
-static int lk_sort_column(DeviceState& ds, const fp256* d_canon, uint32_t u,
+// arrays at the front of s.idx).
+static int lk_sort_column(DeviceState& ds, const LkScratch& s,
+                          const fp256* d_canon, uint32_t u,
                           const int end_bit[4], const uint32_t** perm_out) {
-    uint64_t* keys_in = ds.d_lk_keys.ptr;
+    uint64_t* keys_in = s.keys;
     uint64_t* keys_out = keys_in + u;
-    uint32_t* cur = ds.d_lk_idx.ptr;
+    uint32_t* cur = s.idx;
     uint32_t* nxt = cur + u;
     bool first = true;
     for (uint32_t l = 0; l < 4; l++) {
@@ -271,9 +292,9 @@ static int lk_sort_column(DeviceState& ds, const fp256* d_canon, uint32_t u,
             hipLaunchKernelGGL(k_lk_limb_keys<false>, dim3(lk_blocks(u)),
                                dim3(LK_THREADS), 0, ds.stream,
                                (const uint64_t*)d_canon, l, cur, keys_in, u);
-        size_t tmp = ds.d_lk_tmp.cap;
+        size_t tmp = s.tmp_bytes;
         CUB_TRY(hipcub::DeviceRadixSort::SortPairs(
-            ds.d_lk_tmp.ptr, tmp, keys_in, keys_out, cur, nxt, (int64_t)u, 0,
+            s.tmp, tmp, keys_in, keys_out, cur, nxt, (int64_t)u, 0,
             end_bit[l], ds.stream));
         uint32_t* t = cur;
         cur = nxt;
@@ -292,13 +313,14 @@ int fr_lookup_permute_device(spectre_gpu_ctx* ctx, int dev,
     DeviceState& ds = ctx->devs[dev];
     HIP_TRY(hipSetDevice(ds.device_id));
     const uint32_t u = (uint32_t)u64;  // <= 2^28, checked by the caller
-    RC_TRY(lk_reserve(ds, u));
+    LkScratch s;
+    RC_TRY(lk_reserve(ds, u, s));
     hipStream_t st = ds.stream;
-    fp256* canon_a = ds.d_lk_canon.ptr;  // later: canonical Ss
+    fp256* canon_a = s.canon;  // later: canonical Ss
     fp256* canon_s = canon_a + u;
-    fp256* ss_mont = ds.d_lk_ss.ptr;
-    uint32_t* words = ds.d_lk_words.ptr;
-    uint32_t* notfirst = ds.d_lk_idx.ptr + 2 * (size_t)u;
+    fp256* ss_mont = s.ss;
+    uint32_t* words = s.words;
+    uint32_t* notfirst = s.idx + 2 * (size_t)u;
     uint32_t* free_ = notfirst + u;
     uint32_t* rank_rep = free_ + u;
     uint32_t* rank_left = rank_rep + u;
@@ -312,28 +334,25 @@ int fr_lookup_permute_device(spectre_gpu_ctx* ctx, int dev,
                        dim3(cb < LK_CANON_MAX_BLOCKS ? cb : LK_CANON_MAX_BLOCKS),
                        dim3(LK_THREADS), 0, st, d_input, d_table, canon_a, u,
                        words);
-    HIP_TRY(hipMemcpyAsync(ds.h_lk_words.ptr, words, 8 * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipGetLastError());
+    uint32_t ors[LK_MISS];
+    RC_TRY(call_finish(ds, ors, words, sizeof ors));
     // bits to sort per 64-bit limb; at least one pass, which also builds the
     // identity permutation when every value is zero
     int end_bit[4];
     bool any = false;
     for (int l = 0; l < 4; l++) {
-        const uint64_t w = (uint64_t)ds.h_lk_words.ptr[2 * l] |
-                           (uint64_t)ds.h_lk_words.ptr[2 * l + 1] << 32;
+        const uint64_t w = (uint64_t)ors[2 * l] | (uint64_t)ors[2 * l + 1] << 32;
         end_bit[l] = w ? 64 - __builtin_clzll(w) : 0;
         any |= w != 0;
     }
     if (!any) end_bit[0] = 1;
 
     const uint32_t* perm = nullptr;
-    RC_TRY(lk_sort_column(ds, canon_a, u, end_bit, &perm));
+    RC_TRY(lk_sort_column(ds, s, canon_a, u, end_bit, &perm));
     hipLaunchKernelGGL(k_lk_gather<false>, dim3(nb), dim3(LK_THREADS), 0, st,
                        d_input, (const fp256*)nullptr, perm, d_input_perm,
                        (fp256*)nullptr, u);
-    RC_TRY(lk_sort_column(ds, canon_s, u, end_bit, &perm));
+    RC_TRY(lk_sort_column(ds, s, canon_s, u, end_bit, &perm));
     // canonical A is dead: its half takes the canonical sorted table
     fp256* ss_canon = canon_a;
     hipLaunchKernelGGL(k_lk_gather<true>, dim3(nb), dim3(LK_THREADS), 0, st,
@@ -344,22 +363,20 @@ int fr_lookup_permute_device(spectre_gpu_ctx* ctx, int dev,
     hipLaunchKernelGGL(k_lk_search, dim3(nb), dim3(LK_THREADS), 0, st,
                        (const fp256*)d_input_perm, (const fp256*)ss_canon, u,
                        notfirst, free_, words + LK_MISS);
-    HIP_TRY(hipMemcpyAsync(ds.h_lk_words.ptr + LK_MISS, words + LK_MISS,
-                           sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipGetLastError());
-    if (const uint32_t missing = ds.h_lk_words.ptr[LK_MISS]) {
+    uint32_t missing = 0;
+    RC_TRY(call_finish(ds, &missing, words + LK_MISS, sizeof missing));
+    if (missing) {
         set_err("fr_lookup_permute: lookup miss: %u distinct input value%s "
                 "absent from the table", missing, missing == 1 ? "" : "s");
         return SPECTRE_ERR_LOOKUP_MISS;
     }
 
-    size_t tmp = ds.d_lk_tmp.cap;
-    CUB_TRY(hipcub::DeviceScan::ExclusiveSum(ds.d_lk_tmp.ptr, tmp, notfirst,
-                                             rank_rep, (int)u, st));
-    tmp = ds.d_lk_tmp.cap;
-    CUB_TRY(hipcub::DeviceScan::ExclusiveSum(ds.d_lk_tmp.ptr, tmp, free_,
-                                             rank_left, (int)u, st));
+    size_t tmp = s.tmp_bytes;
+    CUB_TRY(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, notfirst, rank_rep,
+                                             (int)u, st));
+    tmp = s.tmp_bytes;
+    CUB_TRY(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, free_, rank_left,
+                                             (int)u, st));
     hipLaunchKernelGGL(k_lk_first_rows, dim3(nb), dim3(LK_THREADS), 0, st,
                        (const fp256*)d_input_perm, d_table_perm,
                        (const uint32_t*)notfirst, (const uint32_t*)rank_rep,
@@ -369,7 +386,5 @@ int fr_lookup_permute_device(spectre_gpu_ctx* ctx, int dev,
                        (const uint32_t*)rank_left, (const uint32_t*)notfirst,
                        (const uint32_t*)rank_rep, (const uint32_t*)rep,
                        d_table_perm, u);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }

@@ -307,7 +307,8 @@ uint32_t ntt_split(uint32_t log_n, bool force3, uint32_t k[3]) {
 static int build_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
                       bool force3, NttPlan& p) {
     p.npass = ntt_split(log_n, force3, p.k);
-    RC_TRY(pow_tables_build(ds, omega, nullptr, 1u << log_n, p.twB, &p.omega));
+    RC_TRY(p.twB.reserve(pow_table_elems(1u << log_n)));
+    p.omega = pow_tables_build(ds, omega, nullptr, 1u << log_n, p.twB.ptr);
     for (uint32_t i = 0; i < p.npass; i++) {
         fp256 root;  // of axis i's DFT
         ff_pow_u32<NttFr>(root, omega, 1u << (log_n - p.k[i]));
@@ -315,9 +316,7 @@ static int build_plan(DeviceState& ds, const fp256& omega, uint32_t log_n,
         RC_TRY(p.tw[i].reserve(half));
         pow_linear_build(ds, root, p.tw[i].ptr, half);
     }
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }
 
 // build-or-get the cached twiddle plan for (omega, log_n)
@@ -379,11 +378,15 @@ static int ntt_run(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
     const uint32_t n = 1u << log_n;
     NttPlan* plan = nullptr;
     RC_TRY(get_plan(ds, omega, log_n, ctx->ntt_force3, &plan));
-    RC_TRY(ds.d_ntt_tmp.reserve(n));
-    fp256* const tmp = ds.d_ntt_tmp.ptr;
+    ScratchLayout lay;
+    const uint64_t o_tmp = lay.add<fp256>(n);
+    const uint64_t o_coset = lay.add<fp256>(coset_gen ? pow_table_elems(n) : 0);
+    RC_TRY(ds.d_call.reserve(lay.total));
+    fp256* const tmp = (fp256*)(ds.d_call.ptr + o_tmp);
     PowTable ctab{};
     if (coset_gen)  // coset power table (per call; tiny)
-        RC_TRY(pow_tables_build(ds, *coset_gen, nullptr, n, ds.d_pow, &ctab));
+        ctab = pow_tables_build(ds, *coset_gen, nullptr, n,
+                                (fp256*)(ds.d_call.ptr + o_coset));
     NttPass pass{};
     pass.omega = plan->omega;
     pass.inverse = inverse ? 1 : 0;
@@ -414,9 +417,7 @@ static int ntt_run(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
         launch_pass(ds.stream, pass, log_n, first ? ext_bits : -1);
         done += plan->k[i];
     }
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }
 
 int ntt_device(spectre_gpu_ctx* ctx, int dev, fp256* d_data, uint32_t log_n,
@@ -440,8 +441,7 @@ int ntt_extend_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
         if (d_out != d_coeffs)
             HIP_TRY(hipMemcpyAsync(d_out, d_coeffs, sizeof(fp256),
                                    hipMemcpyDeviceToDevice, ds.stream));
-        HIP_TRY(hipStreamSynchronize(ds.stream));
-        return 0;
+        return call_finish(ds);
     }
     return ntt_run(ctx, dev, d_coeffs, d_out, log_n + ext_bits, (int)ext_bits,
                    omega_ext, 0, coset_gen);

@@ -39,14 +39,12 @@ int fr_powers_device(spectre_gpu_ctx* ctx, int dev, const fp256& c,
     DeviceState& ds = ctx->devs[dev];
     HIP_TRY(hipSetDevice(ds.device_id));
     if (n == 0) return 0;
-    PowTable tab;
-    RC_TRY(pow_tables_build(ds, g, &c, n, ds.d_pow, &tab));
+    RC_TRY(ds.d_call.reserve(pow_table_elems(n) * sizeof(fp256)));
+    const PowTable tab = pow_tables_build(ds, g, &c, n, (fp256*)ds.d_call.ptr);
     hipLaunchKernelGGL(k_fr_powers,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
                        dim3(THREADS), 0, ds.stream, tab, d_out, n);
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }
 
 // ---- permutation terms -----------------------------------------------------
@@ -115,12 +113,11 @@ int fr_permutation_terms_device(spectre_gpu_ctx* ctx, int dev,
         a.bd[j] = bd;
         ff_mul<PermFr>(bd, bd, delta);
     }
-    PowTable tab;
-    RC_TRY(pow_tables_build(ds, omega, nullptr, n, ds.d_pow, &tab));
+    RC_TRY(ds.d_call.reserve(pow_table_elems(n) * sizeof(fp256)));
+    const PowTable tab =
+        pow_tables_build(ds, omega, nullptr, n, (fp256*)ds.d_call.ptr);
     hipLaunchKernelGGL(k_fr_perm_terms,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
                        dim3(THREADS), 0, ds.stream, a, m, tab, d_num, d_den, n);
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }

@@ -480,9 +480,7 @@ int fr_batch_invert_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_in,
     const uint64_t tile = (uint64_t)POLY_THREADS * e;
     hipLaunchKernelGGL(k_fr_batch_invert, dim3((uint32_t)((n + tile - 1) / tile)),
                        dim3(POLY_THREADS), 0, ds.stream, d_in, d_out, n, e);
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return call_finish(ds);
 }
 
 int fr_grand_product_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_num,
@@ -501,9 +499,9 @@ int fr_grand_product_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_num,
     const uint32_t e = elems_per_thread(ctx);
     const uint64_t tile = (uint64_t)POLY_THREADS * e;
     const uint32_t ntiles = (uint32_t)((n + tile - 1) / tile);
-    RC_TRY(ds.d_gp_prods.reserve((size_t)ntiles + 1));
-    RC_TRY(ds.h_gp_last.reserve(1));
-    fp256* prods = ds.d_gp_prods.ptr;
+    // tile products -> prefixes, the grand total last
+    RC_TRY(ds.d_call.reserve(((size_t)ntiles + 1) * sizeof(fp256)));
+    fp256* prods = (fp256*)ds.d_call.ptr;
     if (d_den)
         hipLaunchKernelGGL(k_gp_ratio<true>, dim3(ntiles), dim3(POLY_THREADS),
                            0, ds.stream, d_num, d_den, d_z, prods, n, e);
@@ -515,13 +513,7 @@ int fr_grand_product_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_num,
     hipLaunchKernelGGL(k_gp_scan, dim3(ntiles), dim3(POLY_THREADS), 0,
                        ds.stream, d_den ? (const fp256*)d_z : d_num, d_z,
                        (const fp256*)prods, n, e);
-    if (out_last)
-        HIP_TRY(hipMemcpyAsync(ds.h_gp_last.ptr, prods + ntiles, sizeof(fp256),
-                               hipMemcpyDeviceToHost, ds.stream));
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    if (out_last) *out_last = *ds.h_gp_last.ptr;
-    return 0;
+    return call_finish(ds, out_last, prods + ntiles, sizeof(fp256));
 }
 
 // The table of x for a launch with e elements per thread; returns x^(256 e),
@@ -563,8 +555,8 @@ int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
                 (unsigned long long)n);
         return -1;
     }
-    RC_TRY(ds.d_poly_parts.reserve((size_t)(npoints * lv.total)));
-    RC_TRY(ds.h_poly_out.reserve(SPECTRE_POLY_EVAL_MAX_POINTS));
+    RC_TRY(ds.d_call.reserve(npoints * lv.total * sizeof(fp256)));
+    fp256* const parts = (fp256*)ds.d_call.ptr;
     fp256 x[SPECTRE_POLY_EVAL_MAX_POINTS];
     for (uint32_t p = 0; p < npoints; p++) x[p] = points[p];
     const fp256* src = d_coeffs;
@@ -573,7 +565,7 @@ int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
         PolyPows pws{};
         for (uint32_t p = 0; p < npoints; p++)
             x[p] = poly_pow_table(pws.pt[p], x[p], e);
-        fp256* dst = ds.d_poly_parts.ptr + npoints * lv.off[l];
+        fp256* dst = parts + npoints * lv.off[l];
         // the coefficients serve every point; above them, a vector per point
         const uint32_t ny = l == 0 ? 1 : npoints;
         hipLaunchKernelGGL(k_poly_tile_eval, dim3(poly_tiles(m, tile), ny),
@@ -583,12 +575,7 @@ int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
         m = lv.size[l];
     }
     // the last level is one element per point, contiguous
-    HIP_TRY(hipMemcpyAsync(ds.h_poly_out.ptr, src, npoints * sizeof(fp256),
-                           hipMemcpyDeviceToHost, ds.stream));
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    for (uint32_t p = 0; p < npoints; p++) out[p] = ds.h_poly_out.ptr[p];
-    return 0;
+    return call_finish(ds, out, src, npoints * sizeof(fp256));
 }
 
 int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
@@ -613,9 +600,8 @@ int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
                 (unsigned long long)n);
         return -1;
     }
-    RC_TRY(ds.d_poly_parts.reserve((size_t)lv.total + 1));
-    RC_TRY(ds.h_poly_out.reserve(SPECTRE_POLY_EVAL_MAX_POINTS));
-    fp256* parts = ds.d_poly_parts.ptr;
+    RC_TRY(ds.d_call.reserve((lv.total + 1) * sizeof(fp256)));
+    fp256* parts = (fp256*)ds.d_call.ptr;
     fp256* d_rem = parts + lv.total;
     // vec[0] = a, vec[l] = the partials of vec[l - 1], at the point zl[l]
     const fp256* vec[POLY_MAX_LEVELS + 1];
@@ -643,11 +629,5 @@ int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
                            top ? (const fp256*)nullptr : vec[l + 1], len[l],
                            top ? d_rem : (fp256*)nullptr, e, zl[l]);
     }
-    if (out_rem)
-        HIP_TRY(hipMemcpyAsync(ds.h_poly_out.ptr, d_rem, sizeof(fp256),
-                               hipMemcpyDeviceToHost, ds.stream));
-    HIP_TRY(hipStreamSynchronize(ds.stream));
-    HIP_TRY(hipGetLastError());
-    if (out_rem) *out_rem = *ds.h_poly_out.ptr;
-    return 0;
+    return call_finish(ds, out_rem, d_rem, sizeof(fp256));
 }

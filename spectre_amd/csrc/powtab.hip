@@ -74,15 +74,13 @@ static void pow_launch(DeviceState& ds, const fp256& g, const PowRange& a,
                        ds.stream, pw, a, b, nba);
 }
 
-int pow_tables_build(DeviceState& ds, const fp256& g, const fp256* scale,
-                     uint64_t n, DevBuf<fp256>& buf, PowTable* t) {
+PowTable pow_tables_build(DeviceState& ds, const fp256& g, const fp256* scale,
+                          uint64_t n, fp256* dst) {
     const uint32_t t1n = n < POW_LOW ? (uint32_t)n : POW_LOW;
-    const uint32_t t2n = (uint32_t)((n + POW_LOW - 1) >> POW_LOW_BITS);
-    RC_TRY(buf.reserve((size_t)POW_LOW + t2n));
-    *t = PowTable{buf.ptr, buf.ptr + POW_LOW};
-    pow_launch(ds, g, pow_range(buf.ptr, t1n, 0, nullptr),
-               pow_range(buf.ptr + POW_LOW, t2n, POW_LOW_BITS / 2, scale));
-    return 0;
+    const uint32_t t2n = (uint32_t)(pow_table_elems(n) - POW_LOW);
+    pow_launch(ds, g, pow_range(dst, t1n, 0, nullptr),
+               pow_range(dst + POW_LOW, t2n, POW_LOW_BITS / 2, scale));
+    return PowTable{dst, dst + POW_LOW};
 }
 
 void pow_linear_build(DeviceState& ds, const fp256& g, fp256* out,

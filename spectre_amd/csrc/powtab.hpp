@@ -2,15 +2,14 @@
 // and exponents e < n <= 2^28:
 //   g^e = T1[e & 0xfff] * T2[e >> 12]      (one multiply, two cached loads)
 // T1 holds g^j, j < min(n, 4096); T2 holds scale * g^(4096 j), j <
-// ceil(n / 4096). Both live in one DevBuf, and T2 starts at ptr + POW_LOW
-// whatever n is (T1 entries from n up are neither written nor read). The
-// NTT's twiddle and coset factors and the permutation argument's row powers
-// resolve through it. Included by internal.hpp, ahead of DevBuf.
+// ceil(n / 4096). Both live in one run of pow_table_elems(n) elements
+// (scratch.hpp), and T2 starts at element POW_LOW whatever n is (T1 entries
+// from n up are neither written nor read). The NTT's twiddle and coset
+// factors and the permutation argument's row powers resolve through it.
 #pragma once
 #include "ff.hpp"
+#include "scratch.hpp"
 
-#define POW_LOW_BITS 12
-#define POW_LOW (1u << POW_LOW_BITS)
 #define POW_LOW_MASK (POW_LOW - 1u)
 
 struct PowTable { const fp256 *T1, *T2; };
@@ -22,12 +21,12 @@ __device__ __forceinline__ void pow_lookup(fp256& o, const PowTable& t,
 }
 
 struct DeviceState;
-template <typename T, bool kPinned> struct DevBuf;
 // powtab.hip — both enqueue one launch on ds.stream and do not synchronize.
-// The table of g for exponents < n (1 <= n <= 2^28) into buf, grown as
-// needed; *t = its two halves. A null scale is 1.
-int pow_tables_build(DeviceState& ds, const fp256& g, const fp256* scale,
-                     uint64_t n, DevBuf<fp256, false>& buf, PowTable* t);
+// The table of g for exponents < n (1 <= n <= 2^28) into the
+// pow_table_elems(n) elements at dst; returns its two halves. A null scale
+// is 1.
+PowTable pow_tables_build(DeviceState& ds, const fp256& g, const fp256* scale,
+                          uint64_t n, fp256* dst);
 // out[j] = g^j, j < count, 1 <= count <= 2^28
 void pow_linear_build(DeviceState& ds, const fp256& g, fp256* out,
                       uint32_t count);

@@ -353,6 +353,131 @@ def test_ntt_and_permutation_calls_share_one_table_buffer(oracle, columns):
         d.g.close()
 
 
+def test_every_synchronous_call_shares_one_scratch_arena(oracle, columns):
+    """All device scratch of the synchronous Fr calls is carved out of one
+    per-device arena, and their small readbacks land in one pinned block. One
+    context of its own (the arena starts empty, so the growth order is known):
+    calls that grow the arena, which moves it, reuse it at a smaller need and
+    hand the pinned block from one user to the next. Every result byte-exact
+    against the oracle, permutation_ref, lookup_permute_ref or Python
+    integers; every guard element untouched."""
+    from spectre_amd import SpectreGpu
+    lp = _load("lookup_permute_ref")
+    rng = random.Random(0xa7e4a)
+    data = oracle.gen_fr_vector(1 << 15, seed=0xa7e4b)
+    vals = pr.ints(data[:32 * 4100])
+    g5 = pr.enc(5)
+    d = Dev(SpectreGpu([0]))
+    G = d.g
+    try:
+        def ntt(log_n, coset_gen):
+            src, w = data[:32 << log_n], pr.enc(root(log_n))
+            p = d.put(src)
+            G.ntt_device(p, log_n, w, coset_gen=coset_gen)
+            assert d.get(p, 1 << log_n) == oracle.ntt(
+                src, log_n, w, coset_gen=coset_gen), f"NTT 2^{log_n}"
+
+        def lookup(a, s):
+            u = len(a)
+            a_b, s_b = lp.mont(a), lp.mont(s)
+            d_a, d_s = d.put(a_b), d.put(s_b)
+            d_ap, d_sp = d.out(u), d.out(u)
+            try:
+                G.fr_lookup_permute(d_a, d_s, d_ap, d_sp, u)
+            finally:
+                got = (d.get_guarded(d_ap, u, "d_input_perm"),
+                       d.get_guarded(d_sp, u, "d_table_perm"))
+                assert d.get(d_a, u) == a_b and d.get(d_s, u) == s_b
+            return got
+
+        def poly_eval(n, points):
+            got = G.fr_poly_eval(d.put(data[:32 * n]), n,
+                                 [pr.enc(x) for x in points])
+            for x, y in zip(points, got):
+                acc = 0
+                for c in reversed(vals[:n]):
+                    acc = (acc * x + c) % R
+                assert y == pr.enc(acc), f"fr_poly_eval n={n} at {x:#x}"
+
+        # 1: tmp and the coset table, two passes
+        ntt(13, g5)
+        # 2: three tiles of products; the total comes back through the block
+        n = 2049
+        num, den = vals[:n], vals[n:2 * n]
+        z0 = rng.randrange(1, R)
+        want_z = [z0]
+        for i in range(n):
+            want_z.append(want_z[i] * num[i] % R * pr.inv0(den[i]) % R)
+        d_z = d.out(n)
+        last = G.fr_grand_product(d.put(pr.mont(num)), d.put(pr.mont(den)),
+                                  pr.enc(z0), d_z, n)
+        assert d.get_guarded(d_z, n, "d_z") == pr.mont(want_z[:n])
+        assert last == pr.enc(want_z[n])
+        # 3: six extents and hipCUB temp storage: the arena grows and moves
+        u = 4097
+        table = [vals[rng.randrange(u // 3)] for _ in range(u)]
+        inputs = [table[rng.randrange(u)] for _ in range(u)]
+        want_a, want_s = lp.serial(inputs, table)
+        want_lookup = (lp.mont(want_a), lp.mont(want_s))
+        assert lookup(inputs, table) == want_lookup
+        # 4: the cached plan's tables are not in the arena and survived
+        ntt(13, g5)
+        # 5: two levels of partials; evaluations and remainder read back
+        n = 1025
+        points = [rng.randrange(2, R) for _ in range(3)]
+        poly_eval(n, points)
+        z = rng.randrange(2, R)
+        want_q = [0] * n
+        for i in range(n - 2, -1, -1):
+            want_q[i] = (vals[i + 1] + z * want_q[i + 1]) % R
+        d_q = d.out(n)
+        rem = G.fr_poly_div_linear(d.put(data[:32 * n]), pr.enc(z), d_q, n)
+        assert d.get_guarded(d_q, n, "d_q") == pr.mont(want_q)
+        assert rem == pr.enc((vals[0] + z * want_q[0]) % R)
+        # 6: one input value the table does not hold
+        absent = vals[u // 3]  # the table draws from the values before it
+        assert absent not in table
+        with pytest.raises(RuntimeError,
+                           match=r"rc=-5: .*lookup miss: 1 distinct input "
+                                 r"value absent"):
+            lookup(inputs[:-1] + [absent], table)
+        # 7: the pinned block goes from the miss count to evaluations
+        poly_eval(n, points)
+        # 8: the row-power table, twice
+        m, n, omega = 2, 4097, root(13)
+        beta, gamma = columns["beta"], columns["gamma"]
+        values = [c[:n] for c in columns["values"][:m]]
+        sigmas = [c[:n] for c in columns["sigmas"][:m]]
+        d_in = [d.put(pr.mont(c)) for c in values + sigmas]
+        d_num, d_den = d.out(n), d.out(n)
+        G.fr_permutation_terms(d_in[:m], d_in[m:], pr.enc(beta),
+                               pr.enc(gamma), pr.enc(omega), None,
+                               pr.enc(DELTA), d_num, d_den, n)
+        want_num, want_den = pr.terms(values, sigmas, beta, gamma, omega, 1,
+                                      DELTA, n)
+        assert d.get_guarded(d_num, n, "d_num") == pr.mont(want_num)
+        assert d.get_guarded(d_den, n, "d_den") == pr.mont(want_den)
+        c, g = rng.randrange(1, R), rng.randrange(2, R)
+        assert gpu_powers(d, c, g, n) == pr.mont(pr.powers(c, g, n))
+        # 9: column pointers, one constant and the program, staged
+        n, k = 256, rng.randrange(1, R)
+        d_res = d.out(n)
+        G.gate_eval([d.put(data[:32 * n]), d.put(data[32 * n:64 * n])],
+                    pr.enc(k),
+                    [(G.GATE_COL, 0, 0), (G.GATE_COL, 1, 0),
+                     (G.GATE_MUL, 0, 0), (G.GATE_CONST, 0, 0),
+                     (G.GATE_ADD, 0, 0)], n, rot_scale=1, d_out=d_res)
+        assert d.get_guarded(d_res, n, "gate_eval") == pr.mont(
+            [(a * b + k) % R for a, b in zip(vals[:n], vals[n:2 * n])])
+        # 10: the arena grows again
+        ntt(15, None)
+        # 11: reuse at a smaller need
+        assert lookup(inputs, table) == want_lookup
+    finally:
+        d.free()
+        d.g.close()
+
+
 # ------------------------------------------------------------ argument checks
 def test_argument_checks(dev, gpu, columns):
     n = 300
