@@ -4,7 +4,9 @@
  * ops (quotient phase), batch inverse and grand product (Z columns), the
  * lookup argument's sorted input and permuted table columns, the permutation
  * argument's grand-product terms and row-power columns, and polynomial
- * evaluation and (X - z) division (opening phase).
+ * evaluation and (X - z) division (opening phase), with the set-level forms
+ * a multiopen argument loops over: a linear combination of up to 32
+ * polynomials, their evaluation at one point set, and division by the set.
  *
  * This is the drop-in boundary for the Spectre/halo2 proving hot path: the
  * reference's own seam is the pair of free functions
@@ -323,6 +325,56 @@ int spectre_gpu_fr_poly_eval(spectre_gpu_ctx*, int dev, const void* d_coeffs,
 int spectre_gpu_fr_poly_div_linear(spectre_gpu_ctx*, int dev, const void* d_a,
                                    const uint8_t z[32], void* d_q, uint64_t n,
                                    uint8_t out_rem[32]);
+
+/* The set-level forms of the two calls above and of the ADD_SCALED chain
+ * around them: what SHPLONK / GWC do per rotation set in one call each.
+ * Serialized and synchronizing like their neighbours; a rejected call writes
+ * nothing. Both batched calls take at most SPECTRE_OPEN_MAX_POLYS
+ * polynomials; a longer sum is chained through the accumulator (below). */
+#define SPECTRE_OPEN_MAX_POLYS 32u
+/* out[i] = sum_{k<m} coeffs[k] * polys[k][i]   for i < n.
+ * d_polys: HOST array of m DEVICE pointers, n elements each. coeffs: host,
+ * m*32 B. 1 <= m <= MAX_POLYS, n <= 2^28; n == 0 does nothing. d_out may
+ * EQUAL any of the inputs and one pointer may be listed several times: to
+ * accumulate, or to chain past MAX_POLYS, list the accumulator with
+ * coefficient one. Any other overlap of d_out with an input is refused, as
+ * is a NULL entry. Exactly n elements are written; inputs are never written.
+ * The sum is exact, so the bytes are those of halo2's Horner in y. */
+int spectre_gpu_fr_lincomb(spectre_gpu_ctx*, int dev,
+                           const void* const* d_polys, const uint8_t* coeffs,
+                           uint32_t m, void* d_out, uint64_t n);
+/* out[k*npoints + p] = sum_{i<n} polys[k][i] * points[p]^i: every polynomial
+ * of a rotation set at the set's points, one read of each polynomial and one
+ * synchronization. d_polys: HOST array of m DEVICE pointers, n elements
+ * each; one pointer may be listed twice. points: host, npoints*32 B. out:
+ * host, m*npoints*32 B. 1 <= m <= MAX_POLYS, 1 <= npoints <=
+ * SPECTRE_POLY_EVAL_MAX_POINTS, n <= 2^28; n == 0: every output is zero.
+ * Inputs are never written. */
+int spectre_gpu_fr_poly_eval_batch(spectre_gpu_ctx*, int dev,
+                                   const void* const* d_polys, uint32_t m,
+                                   uint64_t n, const uint8_t* points,
+                                   uint32_t npoints, uint8_t* out);
+/* spectre_gpu_fr_poly_div_linear applied nroots times, in the order of
+ * `roots`, with one synchronization: the first division goes d_a -> d_q, the
+ * rest run in place in d_q; out_rems[j] is the remainder of division j.
+ * roots: host, nroots*32 B. out_rems: host, nroots*32 B, or NULL.
+ * 1 <= nroots <= 8, n <= 2^28. d_q may equal d_a (any other overlap is
+ * refused); out of place d_a is not written. n == 0: the remainders are
+ * zero and nothing is written. No inverse is taken: repeated roots, 0 and 1
+ * are ordinary inputs. What follows from the definition, with
+ * Z_S = prod_j (X - roots[j]):
+ *   quotient    q is the quotient of a by Z_S; the top min(nroots, n)
+ *               elements of d_q are zero.
+ *   remainders  they are the Newton coefficients of the remainder:
+ *                 a = Z_S * q + sum_j rems[j] * prod_{i<j} (X - roots[i])
+ *   no r_i      a multiopen prover need not subtract the interpolant r_i of
+ *               f_i's evaluations over S before dividing: the quotient of
+ *               f_i by Z_S already is (f_i - r_i) / Z_S.
+ *   a check     out_rems is r_i in Newton form over the roots in order, so
+ *               the caller can assert it against its own interpolation. */
+int spectre_gpu_fr_poly_div_roots(spectre_gpu_ctx*, int dev, const void* d_a,
+                                  const uint8_t* roots, uint32_t nroots,
+                                  void* d_q, uint64_t n, uint8_t* out_rems);
 
 /* ---- lookup argument (device buffers, Montgomery Fr) ---------------------
  * halo2's permute_expression_pair over the u usable rows of a lookup's

@@ -716,6 +716,120 @@ int spectre_gpu_fr_poly_div_linear(spectre_gpu_ctx* ctx, int dev,
     return 0;
 }
 
+// a host array of m device pointers, 1 <= m <= SPECTRE_OPEN_MAX_POLYS, none
+// of them null
+static int check_poly_list(const char* what, const void* const* d_polys,
+                           uint32_t m) {
+    if (m < 1 || m > SPECTRE_OPEN_MAX_POLYS) {
+        set_err("%s: m %u outside [1, %u]", what, m, SPECTRE_OPEN_MAX_POLYS);
+        return -1;
+    }
+    if (!d_polys) {
+        set_err("%s: null pointer array", what);
+        return -1;
+    }
+    for (uint32_t k = 0; k < m; k++) {
+        if (!d_polys[k]) {
+            set_err("%s: null device pointer d_polys[%u]", what, k);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+int spectre_gpu_fr_lincomb(spectre_gpu_ctx* ctx, int dev,
+                           const void* const* d_polys, const uint8_t* coeffs,
+                           uint32_t m, void* d_out, uint64_t n) {
+    if (check_dev(ctx, dev)) return -1;
+    RC_TRY(check_poly_list("fr_lincomb", d_polys, m));
+    if (!coeffs) {
+        set_err("fr_lincomb: null coeffs");
+        return -1;
+    }
+    if (n > (1ull << 28)) {
+        set_err("fr_lincomb: n %llu > 2^28", (unsigned long long)n);
+        return -1;
+    }
+    if (n == 0) return 0;
+    if (!d_out) {
+        set_err("fr_lincomb: null device pointer d_out");
+        return -1;
+    }
+    // d_out is an input or lies clear of its n elements
+    for (uint32_t k = 0; k < m; k++) {
+        if (d_polys[k] != d_out &&
+            ranges_overlap(d_polys[k], 32 * n, d_out, 32 * n)) {
+            set_err("fr_lincomb: d_out overlaps d_polys[%u] without being "
+                    "equal", k);
+            return -1;
+        }
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 cv[SPECTRE_OPEN_MAX_POLYS];
+    for (uint32_t k = 0; k < m; k++) ff_from_bytes(cv[k], coeffs + 32 * k);
+    return fr_lincomb_device(ctx, dev, (const fp256* const*)d_polys, cv, m,
+                             (fp256*)d_out, n);
+}
+
+int spectre_gpu_fr_poly_eval_batch(spectre_gpu_ctx* ctx, int dev,
+                                   const void* const* d_polys, uint32_t m,
+                                   uint64_t n, const uint8_t* points,
+                                   uint32_t npoints, uint8_t* out) {
+    if (check_dev(ctx, dev)) return -1;
+    RC_TRY(check_poly_list("fr_poly_eval_batch", d_polys, m));
+    if (!points || !out) {
+        set_err("fr_poly_eval_batch: null points/out");
+        return -1;
+    }
+    if (npoints < 1 || npoints > SPECTRE_POLY_EVAL_MAX_POINTS) {
+        set_err("fr_poly_eval_batch: npoints %u outside [1, %u]", npoints,
+                SPECTRE_POLY_EVAL_MAX_POINTS);
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 pts[SPECTRE_POLY_EVAL_MAX_POINTS];
+    std::vector<fp256> vals((size_t)m * npoints);
+    for (uint32_t p = 0; p < npoints; p++) ff_from_bytes(pts[p], points + 32 * p);
+    RC_TRY(fr_poly_eval_batch_device(ctx, dev, (const fp256* const*)d_polys, m,
+                                     n, pts, npoints, vals.data()));
+    for (size_t v = 0; v < vals.size(); v++) ff_to_bytes(out + 32 * v, vals[v]);
+    return 0;
+}
+
+int spectre_gpu_fr_poly_div_roots(spectre_gpu_ctx* ctx, int dev,
+                                  const void* d_a, const uint8_t* roots,
+                                  uint32_t nroots, void* d_q, uint64_t n,
+                                  uint8_t* out_rems) {
+    if (check_dev(ctx, dev)) return -1;
+    if (!d_a || !d_q || !roots) {
+        set_err("fr_poly_div_roots: null %s",
+                roots ? "device pointer" : "roots");
+        return -1;
+    }
+    if (nroots < 1 || nroots > SPECTRE_POLY_EVAL_MAX_POINTS) {
+        set_err("fr_poly_div_roots: nroots %u outside [1, %u]", nroots,
+                SPECTRE_POLY_EVAL_MAX_POINTS);
+        return -1;
+    }
+    if (n > (1ull << 28)) {
+        set_err("fr_poly_div_roots: n %llu > 2^28", (unsigned long long)n);
+        return -1;
+    }
+    if (d_a != d_q && ranges_overlap(d_a, 32 * n, d_q, 32 * n)) {
+        set_err("fr_poly_div_roots: d_q overlaps d_a without being equal");
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    fp256 zs[SPECTRE_POLY_EVAL_MAX_POINTS], rems[SPECTRE_POLY_EVAL_MAX_POINTS];
+    for (uint32_t j = 0; j < nroots; j++) ff_from_bytes(zs[j], roots + 32 * j);
+    RC_TRY(fr_poly_div_roots_device(ctx, dev, (const fp256*)d_a, zs, nroots,
+                                    (fp256*)d_q, n,
+                                    out_rems ? rems : nullptr));
+    for (uint32_t j = 0; out_rems && j < nroots; j++)
+        ff_to_bytes(out_rems + 32 * j, rems[j]);
+    return 0;
+}
+
 // ---------------------------------------------------------------- lookup argument
 int spectre_gpu_fr_lookup_permute(spectre_gpu_ctx* ctx, int dev,
                                   const void* d_input, const void* d_table,

@@ -1,6 +1,6 @@
 // gate.hip — quotient-phase glue over Fr: the gate-expression evaluator and
 // the pointwise vector ops, the periodic multiply of divide_by_vanishing_poly
-// among them.
+// and the opening phase's linear combination among them.
 //
 // The kernels compute in GateFr, Fr with the C CIOS multiply, the choice they
 // were written and measured under; none has been timed with the asm
@@ -199,6 +199,68 @@ int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                        dim3((uint32_t)((n + THREADS - 1) / THREADS)),
                        dim3(THREADS), 0, ds.stream, op, d_a, d_b, cv, d_out,
                        n);
+    return call_finish(ds);
+}
+
+// ---- out[i] = sum_k c[k] * p[k][i] (multiopen's sums in y and v) -----------
+// The pointers and coefficients travel in the kernel arguments (32 * 8 +
+// 32 * 32 = 1280 B), so nothing is staged. Row i runs in lane i, two 16-byte
+// loads per element; the column loop is wave-uniform to the run-time m and
+// the accumulator stays in registers: no LDS, no scratch. The kernel
+// streams, so what matters is the loads in flight per lane: the loop takes
+// LINCOMB_AHEAD polynomials per trip and issues all their loads before the
+// first multiply (1 = a round trip to memory per polynomial). Measured, 1, 2
+// and 4 are within 1 % of each other at m = 8 and 32 (eight waves per SIMD
+// already keep the memory system busy); 2 is kept for m = 2, where it is up
+// to 5 % ahead, at 54 VGPRs; 8 spills (DESIGN.md "Multiopen"). out may equal
+// any input (hence no __restrict__): a lane reads row i of every input
+// before it writes row i, and touches no other row.
+#ifndef LINCOMB_AHEAD
+#define LINCOMB_AHEAD 2
+#endif
+struct LincombArgs {
+    const fp256* p[SPECTRE_OPEN_MAX_POLYS];
+    fp256 c[SPECTRE_OPEN_MAX_POLYS];
+};
+__global__ __launch_bounds__(THREADS) void k_fr_lincomb(
+    LincombArgs a, uint32_t m, fp256* out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fp256 acc;
+    ff_set_zero(acc);
+#pragma unroll 1
+    for (uint32_t k0 = 0; k0 < m; k0 += LINCOMB_AHEAD) {
+        fp256 v[LINCOMB_AHEAD];
+#pragma unroll
+        for (uint32_t j = 0; j < LINCOMB_AHEAD; j++)
+            if (k0 + j < m) v[j] = a.p[k0 + j][i];
+#pragma unroll
+        for (uint32_t j = 0; j < LINCOMB_AHEAD; j++) {
+            if (k0 + j < m) {
+                fp256 t;
+                ff_mul<GateFr>(t, v[j], a.c[k0 + j]);
+                ff_add<GateFr>(acc, acc, t);
+            }
+        }
+    }
+    out[i] = acc;
+}
+
+int fr_lincomb_device(spectre_gpu_ctx* ctx, int dev,
+                      const fp256* const* d_polys, const fp256* coeffs,
+                      uint32_t m, fp256* d_out, uint64_t n) {
+    DeviceState& ds = ctx->devs[dev];
+    HIP_TRY(hipSetDevice(ds.device_id));
+    if (n == 0) return 0;
+    LincombArgs a;
+    for (uint32_t k = 0; k < SPECTRE_OPEN_MAX_POLYS; k++) {
+        a.p[k] = k < m ? d_polys[k] : nullptr;
+        if (k < m) a.c[k] = coeffs[k];
+        else ff_set_zero(a.c[k]);
+    }
+    hipLaunchKernelGGL(k_fr_lincomb,
+                       dim3((uint32_t)((n + THREADS - 1) / THREADS)),
+                       dim3(THREADS), 0, ds.stream, a, m, d_out, n);
     return call_finish(ds);
 }
 

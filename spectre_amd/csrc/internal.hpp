@@ -200,7 +200,9 @@ struct DeviceState {
 // The one epilogue of a synchronous device call: if dst is given, enqueue
 // the readback of bytes <= CALL_PINNED_BYTES from d_src into h_call; then
 // synchronize the stream, surface a launch error, and copy the bytes out.
-#define CALL_PINNED_BYTES 256  // eight fp256
+// The largest readback is fr_poly_eval_batch's: 32 polynomials at 8 points.
+#define CALL_PINNED_BYTES \
+    (SPECTRE_OPEN_MAX_POLYS * SPECTRE_POLY_EVAL_MAX_POINTS * 32u)
 inline int call_finish(DeviceState& ds, void* dst = nullptr,
                        const void* d_src = nullptr, size_t bytes = 0) {
     if (dst) {
@@ -274,6 +276,12 @@ int fr_gate_eval_device(spectre_gpu_ctx* ctx, int dev,
 int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                      const fp256* d_b, const fp256* c, fp256* d_out,
                      uint64_t n);
+// gate.hip — out[i] = sum_k coeffs[k] * polys[k][i] over the 1..
+// SPECTRE_OPEN_MAX_POLYS device pointers of the host array d_polys
+// (synchronizes). d_out may equal any of them.
+int fr_lincomb_device(spectre_gpu_ctx* ctx, int dev,
+                      const fp256* const* d_polys, const fp256* coeffs,
+                      uint32_t m, fp256* d_out, uint64_t n);
 // gate.hip — out[i] = a[i] * table[i mod period], table = `period` host
 // elements, period a power of two <= SPECTRE_VEC_PERIOD_MAX (synchronizes).
 // d_out may alias d_a.
@@ -314,6 +322,19 @@ int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
 int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
                               const fp256& z, fp256* d_q, uint64_t n,
                               fp256* out_rem);
+// poly.hip — out[k * npoints + p] = sum_i polys[k][i] * points[p]^i for the
+// 1..SPECTRE_OPEN_MAX_POLYS device pointers of the host array d_polys and
+// 1..8 host points, one read of each polynomial (synchronizes).
+int fr_poly_eval_batch_device(spectre_gpu_ctx* ctx, int dev,
+                              const fp256* const* d_polys, uint32_t npolys,
+                              uint64_t n, const fp256* points,
+                              uint32_t npoints, fp256* out);
+// poly.hip — fr_poly_div_linear_device by roots[0..nroots) in turn, 1 <=
+// nroots <= 8: d_a -> d_q, then in place in d_q; out_rems (may be null) =
+// the nroots remainders (synchronizes once). d_q may alias d_a.
+int fr_poly_div_roots_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
+                             const fp256* roots, uint32_t nroots, fp256* d_q,
+                             uint64_t n, fp256* out_rems);
 // poly.hip — the built-in tile of the calls above, and whether a
 // ctx->fr_scan_tile value is usable (pure; host).
 uint32_t fr_scan_tile_default();

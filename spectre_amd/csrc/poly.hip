@@ -64,6 +64,14 @@
 // neither on the tile size nor on the association order. A thread reads all
 // of a[f, f+e) before it writes q[f, f+e) and touches no other index of
 // either, which is what lets d_q alias d_a.
+//
+// Set-level forms (multiopen). fr_poly_eval_batch is the evaluation above
+// with a third grid dimension: z is the polynomial, taken at the first level
+// from a pointer table in the kernel arguments, and every level runs the
+// partial vectors of all m polynomials and all points in one launch, so the
+// launches per call do not grow with m and one readback returns m * npoints
+// values. fr_poly_div_roots enqueues the division above once per root, the
+// first from d_a and the rest in place in d_q, and synchronizes once.
 #include "internal.hpp"
 #include "poly_levels.hpp"
 
@@ -384,21 +392,22 @@ __device__ __forceinline__ void wtree_down(uint4* lds4, uint32_t t,
     }
 }
 
-// Tile partials. Block (b, y) reads tile b of the n-element vector
-// src + y * src_stride once and, for each of its ppb points
-// p = y * ppb + j, writes sum_k src[bT + k] x_p^k to
-// partials[p * part_stride + b]. The first level runs one y with all the
-// points (one read of the coefficients), the levels above one point per y.
-__global__ __launch_bounds__(POLY_THREADS) void k_poly_tile_eval(
-    const fp256* __restrict__ src, uint64_t src_stride, uint64_t n,
+// Tile partials. Block (b, y, z) works for polynomial z of a batch (one, z =
+// 0, outside fr_poly_eval_batch) and the ppb points p = y * ppb + j of the
+// call's npts = gridDim.y * ppb: it reads tile b of its n-element vector src
+// once and, for each p, writes sum_k src[bT + k] x_p^k to row z * npts + p of
+// partials, at column b. The POINT table is indexed by p alone, the partial
+// VECTOR by (z, p).
+__device__ __forceinline__ void poly_tile_eval(
+    uint4* lds4, const fp256* __restrict__ src, uint64_t n,
     fp256* __restrict__ partials, uint64_t part_stride, uint32_t ppb,
-    uint32_t e, const PolyPows pws) {
-    __shared__ uint4 lds4[2 * POLY_H];
+    uint32_t e, const PolyPows& pws) {
     const uint32_t t = threadIdx.x;
     const uint64_t first = ((uint64_t)blockIdx.x * POLY_THREADS + t) * e;
     const int64_t cnt = (int64_t)n - (int64_t)first;
+    const uint32_t row0 = blockIdx.z * gridDim.y * ppb;
     fp256 a[POLY_E_MAX];
-    load_own_zero(a, src + blockIdx.y * src_stride + first, cnt, e);
+    load_own_zero(a, src + first, cnt, e);
     for (uint32_t j = 0; j < ppb; j++) {
         const uint32_t p = blockIdx.y * ppb + j;
         const PolyPow& pw = pws.pt[p];
@@ -407,9 +416,37 @@ __global__ __launch_bounds__(POLY_THREADS) void k_poly_tile_eval(
         wtree_up(lds4, t, s, pw);
         if (t == 0) {
             lds_split_ld(lds4, 1, POLY_H, s);
-            partials[p * part_stride + blockIdx.x] = s;
+            partials[(uint64_t)(row0 + p) * part_stride + blockIdx.x] = s;
         }
     }
+}
+
+// The vectors lie src_stride apart, one per (z, y): the first level of
+// fr_poly_eval runs one y with all the points (one read of the
+// coefficients); the levels above it, in the batch too, one point per y, each
+// on the partial vector of its own (z, p).
+__global__ __launch_bounds__(POLY_THREADS) void k_poly_tile_eval(
+    const fp256* __restrict__ src, uint64_t src_stride, uint64_t n,
+    fp256* __restrict__ partials, uint64_t part_stride, uint32_t ppb,
+    uint32_t e, const PolyPows pws) {
+    __shared__ uint4 lds4[2 * POLY_H];
+    const uint64_t vec = (uint64_t)blockIdx.z * gridDim.y + blockIdx.y;
+    poly_tile_eval(lds4, src + vec * src_stride, n, partials, part_stride, ppb,
+                   e, pws);
+}
+
+// The first level of a batch: polynomial z comes from a pointer table in the
+// kernel arguments (32 * 8 B beside the 2304 B of powers), one y, all the
+// points.
+struct PolyPtrs {
+    const fp256* p[SPECTRE_OPEN_MAX_POLYS];
+};
+__global__ __launch_bounds__(POLY_THREADS) void k_poly_tile_eval_tab(
+    const PolyPtrs tab, uint64_t n, fp256* __restrict__ partials,
+    uint64_t part_stride, uint32_t ppb, uint32_t e, const PolyPows pws) {
+    __shared__ uint4 lds4[2 * POLY_H];
+    poly_tile_eval(lds4, tab.p[blockIdx.z], n, partials, part_stride, ppb, e,
+                   pws);
 }
 
 // One level of the division: dst[i] = the quotient of the n-element vector
@@ -532,30 +569,35 @@ static uint32_t poly_tiles(uint64_t n, uint64_t tile) {
     return (uint32_t)((n + tile - 1) / tile);
 }
 
-int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
-                        uint64_t n, const fp256* points, uint32_t npoints,
-                        fp256* out) {
+// out[k * npoints + p] = polynomial k at point p, for the one polynomial
+// d_coeffs (npolys = 1) or, d_coeffs null, the npolys of d_polys.
+static int poly_eval_run(spectre_gpu_ctx* ctx, int dev, const char* what,
+                         const fp256* d_coeffs, const fp256* const* d_polys,
+                         uint32_t npolys, uint64_t n, const fp256* points,
+                         uint32_t npoints, fp256* out) {
+    const uint32_t nvec = npolys * npoints;
     if (n > POLY_MAX_N) {
-        set_err("fr_poly_eval: n %llu > 2^28", (unsigned long long)n);
+        set_err("%s: n %llu > 2^28", what, (unsigned long long)n);
         return -1;
     }
     if (n == 0) {
-        for (uint32_t p = 0; p < npoints; p++) ff_set_zero(out[p]);
+        for (uint32_t v = 0; v < nvec; v++) ff_set_zero(out[v]);
         return 0;
     }
     DeviceState& ds = ctx->devs[dev];
     HIP_TRY(hipSetDevice(ds.device_id));
     const uint32_t e = elems_per_thread(ctx);
     const uint64_t tile = (uint64_t)POLY_THREADS * e;
-    // partial vectors down to one element per point; level l holds npoints
-    // vectors of size[l] from element npoints * off[l]
+    // partial vectors down to one element per polynomial and point; level l
+    // holds nvec vectors of size[l] from element nvec * off[l], polynomial
+    // k's at point p being number k * npoints + p
     const PolyLevels lv = poly_levels(n, tile, 1, 1);
     if (!lv.ok) {
-        set_err("fr_poly_eval: level table overflow at n %llu",
+        set_err("%s: level table overflow at n %llu", what,
                 (unsigned long long)n);
         return -1;
     }
-    RC_TRY(ds.d_call.reserve(npoints * lv.total * sizeof(fp256)));
+    RC_TRY(ds.d_call.reserve(nvec * lv.total * sizeof(fp256)));
     fp256* const parts = (fp256*)ds.d_call.ptr;
     fp256 x[SPECTRE_POLY_EVAL_MAX_POINTS];
     for (uint32_t p = 0; p < npoints; p++) x[p] = points[p];
@@ -565,44 +607,50 @@ int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
         PolyPows pws{};
         for (uint32_t p = 0; p < npoints; p++)
             x[p] = poly_pow_table(pws.pt[p], x[p], e);
-        fp256* dst = parts + npoints * lv.off[l];
+        fp256* dst = parts + nvec * lv.off[l];
         // the coefficients serve every point; above them, a vector per point
         const uint32_t ny = l == 0 ? 1 : npoints;
-        hipLaunchKernelGGL(k_poly_tile_eval, dim3(poly_tiles(m, tile), ny),
-                           dim3(POLY_THREADS), 0, ds.stream, src, m, m, dst,
-                           lv.size[l], npoints / ny, e, pws);
+        const dim3 grid(poly_tiles(m, tile), ny, npolys);
+        if (l == 0 && !d_coeffs) {
+            PolyPtrs tab{};
+            for (uint32_t k = 0; k < npolys; k++) tab.p[k] = d_polys[k];
+            hipLaunchKernelGGL(k_poly_tile_eval_tab, grid, dim3(POLY_THREADS),
+                               0, ds.stream, tab, m, dst, lv.size[l],
+                               npoints / ny, e, pws);
+        } else {
+            hipLaunchKernelGGL(k_poly_tile_eval, grid, dim3(POLY_THREADS), 0,
+                               ds.stream, src, m, m, dst, lv.size[l],
+                               npoints / ny, e, pws);
+        }
         src = dst;
         m = lv.size[l];
     }
-    // the last level is one element per point, contiguous
-    return call_finish(ds, out, src, npoints * sizeof(fp256));
+    // the last level is one element per polynomial and point, contiguous
+    return call_finish(ds, out, src, nvec * sizeof(fp256));
 }
 
-int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
-                              const fp256& z, fp256* d_q, uint64_t n,
-                              fp256* out_rem) {
-    if (n > POLY_MAX_N) {
-        set_err("fr_poly_div_linear: n %llu > 2^28", (unsigned long long)n);
-        return -1;
-    }
-    if (n == 0) {
-        if (out_rem) ff_set_zero(*out_rem);
-        return 0;
-    }
-    DeviceState& ds = ctx->devs[dev];
-    HIP_TRY(hipSetDevice(ds.device_id));
-    const uint32_t e = elems_per_thread(ctx);
+int fr_poly_eval_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_coeffs,
+                        uint64_t n, const fp256* points, uint32_t npoints,
+                        fp256* out) {
+    return poly_eval_run(ctx, dev, "fr_poly_eval", d_coeffs, nullptr, 1, n,
+                         points, npoints, out);
+}
+
+int fr_poly_eval_batch_device(spectre_gpu_ctx* ctx, int dev,
+                              const fp256* const* d_polys, uint32_t npolys,
+                              uint64_t n, const fp256* points,
+                              uint32_t npoints, fp256* out) {
+    return poly_eval_run(ctx, dev, "fr_poly_eval_batch", nullptr, d_polys,
+                         npolys, n, points, npoints, out);
+}
+
+// Enqueues one division of the n elements at d_a by (X - z) into d_q (which
+// may be d_a), the remainder into *d_rem; parts = lv.total elements of the
+// arena, free again once the launches have run.
+static void poly_div_enqueue(DeviceState& ds, uint32_t e, const PolyLevels& lv,
+                             fp256* parts, fp256* d_rem, const fp256* d_a,
+                             const fp256& z, fp256* d_q, uint64_t n) {
     const uint64_t tile = (uint64_t)POLY_THREADS * e;
-    // partial vectors until one fits a tile; one more element for a(z)
-    const PolyLevels lv = poly_levels(n, tile, tile, 0);
-    if (!lv.ok) {
-        set_err("fr_poly_div_linear: level table overflow at n %llu",
-                (unsigned long long)n);
-        return -1;
-    }
-    RC_TRY(ds.d_call.reserve((lv.total + 1) * sizeof(fp256)));
-    fp256* parts = (fp256*)ds.d_call.ptr;
-    fp256* d_rem = parts + lv.total;
     // vec[0] = a, vec[l] = the partials of vec[l - 1], at the point zl[l]
     const fp256* vec[POLY_MAX_LEVELS + 1];
     uint64_t len[POLY_MAX_LEVELS + 1];
@@ -629,5 +677,53 @@ int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
                            top ? (const fp256*)nullptr : vec[l + 1], len[l],
                            top ? d_rem : (fp256*)nullptr, e, zl[l]);
     }
-    return call_finish(ds, out_rem, d_rem, sizeof(fp256));
+}
+
+// nroots divisions in a row, the first d_a -> d_q and the rest in place in
+// d_q, sharing the partial vectors (the stream runs them in order) and each
+// with a remainder slot of its own; out_rems (may be null) = nroots elements.
+static int poly_div_run(spectre_gpu_ctx* ctx, int dev, const char* what,
+                        const fp256* d_a, const fp256* roots, uint32_t nroots,
+                        fp256* d_q, uint64_t n, fp256* out_rems) {
+    if (n > POLY_MAX_N) {
+        set_err("%s: n %llu > 2^28", what, (unsigned long long)n);
+        return -1;
+    }
+    if (n == 0) {
+        for (uint32_t j = 0; out_rems && j < nroots; j++)
+            ff_set_zero(out_rems[j]);
+        return 0;
+    }
+    DeviceState& ds = ctx->devs[dev];
+    HIP_TRY(hipSetDevice(ds.device_id));
+    const uint32_t e = elems_per_thread(ctx);
+    const uint64_t tile = (uint64_t)POLY_THREADS * e;
+    // partial vectors until one fits a tile; one more element per a(z)
+    const PolyLevels lv = poly_levels(n, tile, tile, 0);
+    if (!lv.ok) {
+        set_err("%s: level table overflow at n %llu", what,
+                (unsigned long long)n);
+        return -1;
+    }
+    RC_TRY(ds.d_call.reserve((lv.total + nroots) * sizeof(fp256)));
+    fp256* parts = (fp256*)ds.d_call.ptr;
+    fp256* d_rems = parts + lv.total;
+    for (uint32_t j = 0; j < nroots; j++)
+        poly_div_enqueue(ds, e, lv, parts, d_rems + j, j == 0 ? d_a : d_q,
+                         roots[j], d_q, n);
+    return call_finish(ds, out_rems, d_rems, nroots * sizeof(fp256));
+}
+
+int fr_poly_div_linear_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
+                              const fp256& z, fp256* d_q, uint64_t n,
+                              fp256* out_rem) {
+    return poly_div_run(ctx, dev, "fr_poly_div_linear", d_a, &z, 1, d_q, n,
+                        out_rem);
+}
+
+int fr_poly_div_roots_device(spectre_gpu_ctx* ctx, int dev, const fp256* d_a,
+                             const fp256* roots, uint32_t nroots, fp256* d_q,
+                             uint64_t n, fp256* out_rems) {
+    return poly_div_run(ctx, dev, "fr_poly_div_roots", d_a, roots, nroots, d_q,
+                        n, out_rems);
 }

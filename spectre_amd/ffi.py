@@ -174,6 +174,21 @@ def load_library() -> ctypes.CDLL:
         c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64,
         c.c_void_p,
     ]
+    lib.spectre_gpu_fr_lincomb.restype = c.c_int
+    lib.spectre_gpu_fr_lincomb.argtypes = [
+        c.c_void_p, c.c_int, c.POINTER(c.c_void_p), c.c_void_p, c.c_uint32,
+        c.c_void_p, c.c_uint64,
+    ]
+    lib.spectre_gpu_fr_poly_eval_batch.restype = c.c_int
+    lib.spectre_gpu_fr_poly_eval_batch.argtypes = [
+        c.c_void_p, c.c_int, c.POINTER(c.c_void_p), c.c_uint32, c.c_uint64,
+        c.c_void_p, c.c_uint32, c.c_void_p,
+    ]
+    lib.spectre_gpu_fr_poly_div_roots.restype = c.c_int
+    lib.spectre_gpu_fr_poly_div_roots.argtypes = [
+        c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p,
+        c.c_uint64, c.c_void_p,
+    ]
     lib.spectre_gpu_fr_lookup_permute.restype = c.c_int
     lib.spectre_gpu_fr_lookup_permute.argtypes = [
         c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
@@ -591,6 +606,73 @@ class SpectreGpu:
             rem)
         self._check(rc, "fr_poly_div_linear")
         return bytes(rem)
+
+    OPEN_MAX_POLYS = 32  # = SPECTRE_OPEN_MAX_POLYS
+
+    def fr_lincomb(self, d_polys: list[int], coeffs: list[bytes], d_out: int,
+                   n: int, dev: int = 0) -> None:
+        """d_out[i] = sum_k coeffs[k] * d_polys[k][i] for i < n over
+        Montgomery Fr, m = len(d_polys) in 1..OPEN_MAX_POLYS. d_out may equal
+        any input and a pointer may be listed several times (the accumulator
+        with coefficient one chains past OPEN_MAX_POLYS); any other overlap of
+        d_out with an input is refused."""
+        assert len(coeffs) == len(d_polys)
+        assert all(len(c) == 32 for c in coeffs)
+        m = len(d_polys)
+        ptrs = (ctypes.c_void_p * max(1, m))(*d_polys)
+        raw = b"".join(coeffs)
+        cc = (ctypes.c_uint8 * max(32, len(raw))).from_buffer_copy(
+            raw.ljust(32, b"\0"))
+        rc = self._lib.spectre_gpu_fr_lincomb(
+            self._ctx, dev, ptrs, cc, m,
+            ctypes.c_void_p(d_out) if d_out else None, n)
+        self._check(rc, "fr_lincomb")
+
+    def fr_poly_eval_batch(self, d_polys: list[int], n: int,
+                           points: list[bytes],
+                           dev: int = 0) -> list[list[bytes]]:
+        """out[k][p] = sum_i d_polys[k][i] * points[p]^i: the m =
+        len(d_polys) polynomials (1..OPEN_MAX_POLYS, n Montgomery Fr
+        coefficients each) of one rotation set at its 1..8 points, each
+        polynomial read once, one synchronization."""
+        assert all(len(p) == 32 for p in points)
+        m, npts = len(d_polys), len(points)
+        ptrs = (ctypes.c_void_p * max(1, m))(*d_polys)
+        raw = b"".join(points)
+        pts = (ctypes.c_uint8 * max(32, len(raw))).from_buffer_copy(
+            raw.ljust(32, b"\0"))
+        out = (ctypes.c_uint8 * max(32, 32 * m * npts))()
+        rc = self._lib.spectre_gpu_fr_poly_eval_batch(
+            self._ctx, dev, ptrs, m, n, pts, npts, out)
+        self._check(rc, "fr_poly_eval_batch")
+        raw = bytes(out)
+        return [[raw[32 * (k * npts + p):32 * (k * npts + p + 1)]
+                 for p in range(npts)] for k in range(m)]
+
+    def fr_poly_div_roots(self, d_a: int, roots: list[bytes], d_q: int,
+                          n: int, want_rems: bool = True,
+                          dev: int = 0) -> list[bytes] | None:
+        """fr_poly_div_linear by each of the 1..8 roots in turn with one
+        synchronization: d_a -> d_q, then in place in d_q, which ends up
+        holding the quotient of a by Z = prod (X - roots[j]) (its top
+        min(len(roots), n) elements zero). Returns the remainders, which are
+        the Newton coefficients of a mod Z over the roots in order
+        (want_rems False: passes NULL and returns None). d_q may equal
+        d_a."""
+        assert all(len(z) == 32 for z in roots)
+        nroots = len(roots)
+        raw = b"".join(roots)
+        zz = (ctypes.c_uint8 * max(32, len(raw))).from_buffer_copy(
+            raw.ljust(32, b"\0"))
+        rems = (ctypes.c_uint8 * max(32, 32 * nroots))() if want_rems else None
+        rc = self._lib.spectre_gpu_fr_poly_div_roots(
+            self._ctx, dev, ctypes.c_void_p(d_a), zz, nroots,
+            ctypes.c_void_p(d_q), n, rems)
+        self._check(rc, "fr_poly_div_roots")
+        if rems is None:
+            return None
+        raw = bytes(rems)
+        return [raw[32 * j:32 * (j + 1)] for j in range(nroots)]
 
     ERR_LOOKUP_MISS = -5  # = SPECTRE_ERR_LOOKUP_MISS
 

@@ -10,8 +10,16 @@ Every timed call ends in the library's stream synchronize, so a host clock
 around it is the call time. Warm-up calls come first (code-object load and
 scratch allocation), then REPS timed calls; the median and the min..max
 spread are reported. Writes one JSON file (default
-profiles/opening_bench.json) and prints it. Not part of the bench contract
-and not run by the test suite."""
+profiles/opening_bench.json) and prints it.
+
+--multiopen times the set-level calls instead, each against the single calls
+it replaces from the same library in the same process, alternating call by
+call: fr_lincomb at m = 2, 8 and 32 against the SCALE + (m - 1) ADD_SCALED
+chain, fr_poly_eval_batch of 16 polynomials at 1 and 4 points against 16
+fr_poly_eval calls, fr_poly_div_roots at 4 roots against 4 fr_poly_div_linear
+calls (default output profiles/multiopen_bench.json).
+
+Not part of the bench contract and not run by the test suite."""
 import argparse
 import json
 import os
@@ -89,13 +97,135 @@ def entry(ms, n, moved, muls, scale_s):
             "ratio_to_scale": round(med / 1e3 / scale_s, 3)}
 
 
+LINCOMB_M = (2, 8, 32)
+BATCH_POLYS = 16
+BATCH_POINTS = (1, 4)
+DIV_ROOTS = 4
+
+
+def alternating(new, base, reps):
+    """WARMUP calls of each, then reps rounds of (new, base) back to back in
+    one process, so both see the same machine state. Returns (new ms, base
+    ms)."""
+    timed(new, WARMUP)
+    timed(base, WARMUP)
+    t_new, t_base = [], []
+    for _ in range(reps):
+        t_new += timed(new, 1)
+        t_base += timed(base, 1)
+    return t_new, t_base
+
+
+def spread(ms):
+    return {"median_ms": round(statistics.median(ms), 4),
+            "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def pair(t_new, t_base, extra=None):
+    row = {"new": spread(t_new), "baseline": spread(t_base),
+           "reps": len(t_new),
+           "new_over_baseline": round(statistics.median(t_new) /
+                                      statistics.median(t_base), 3)}
+    row.update(extra or {})
+    return row
+
+
+def multiopen_row(gpu, log_n, a, pts):
+    """The set-level calls against the single calls they replace, the same
+    library and process, alternating. The m polynomials are made on the
+    device from one upload (SCALE by different constants)."""
+    n = 1 << log_n
+    m_max = max(LINCOMB_M + (BATCH_POLYS,))
+    d_polys = [gpu.malloc(32 * n) for _ in range(m_max)]
+    d_out, d_q = gpu.malloc(32 * n), gpu.malloc(32 * n)
+    gpu.upload(d_polys[0], a[:32 * n])
+    consts = [a[32 * (16 + k):32 * (17 + k)] for k in range(m_max)]
+    for k in range(1, m_max):
+        gpu.fr_vec_op(gpu.VEC_SCALE, d_polys[0], None, consts[k], d_polys[k],
+                      n)
+    row = {"log_n": log_n}
+
+    def chain(m):
+        gpu.fr_vec_op(gpu.VEC_SCALE, d_polys[0], None, consts[0], d_out, n)
+        for k in range(1, m):
+            gpu.fr_vec_op(gpu.VEC_ADD_SCALED, d_out, d_polys[k], consts[k],
+                          d_out, n)
+
+    for m in LINCOMB_M:
+        t_new, t_base = alternating(
+            lambda m=m: gpu.fr_lincomb(d_polys[:m], consts[:m], d_out, n),
+            lambda m=m: chain(m), REPS)
+        med = statistics.median(t_new)
+        row[f"lincomb_{m}"] = pair(t_new, t_base, {
+            "traffic_ratio": round((m + 1) / (3 * m - 1), 3),
+            "gb_per_s": round(32 * (m + 1) * n / (med / 1e3) / 1e9, 1)})
+    for k in BATCH_POINTS:
+        t_new, t_base = alternating(
+            lambda k=k: gpu.fr_poly_eval_batch(d_polys[:BATCH_POLYS], n,
+                                               pts[:k]),
+            lambda k=k: [gpu.fr_poly_eval(d, n, pts[:k])
+                         for d in d_polys[:BATCH_POLYS]], REPS)
+        row[f"eval_batch_{BATCH_POLYS}x{k}"] = pair(t_new, t_base)
+
+    def div_chain():
+        gpu.fr_poly_div_linear(d_polys[0], pts[0], d_q, n)
+        for z in pts[1:DIV_ROOTS]:
+            gpu.fr_poly_div_linear(d_q, z, d_q, n)
+
+    t_new, t_base = alternating(
+        lambda: gpu.fr_poly_div_roots(d_polys[0], pts[:DIV_ROOTS], d_q, n),
+        div_chain, REPS)
+    row[f"div_roots_{DIV_ROOTS}"] = pair(t_new, t_base)
+    for d in d_polys + [d_out, d_q]:
+        gpu.free(d)
+    return row
+
+
+def main_multiopen(args):
+    gpu = SpectreGpu([0])
+    base = 1 << 16
+    a0 = oracle.gen_fr_vector(base, 21)
+    pts = [a0[32 * i:32 * i + 32] for i in range(8)]
+    results = []
+    for log_n in args.log_sizes:
+        a = a0 * max(1, (1 << log_n) // base)
+        results.append(multiopen_row(gpu, log_n, a, pts))
+    gpu.close()
+    doc = {"tool": "opening_bench --multiopen",
+           "tile": ffi.fr_scan_tile_default(), "warmup": WARMUP,
+           "note": "new = one set-level call, baseline = the single calls it "
+                   "replaces (lincomb_m: SCALE + (m - 1) ADD_SCALED; "
+                   "eval_batch_16xk: 16 fr_poly_eval at k points; "
+                   "div_roots_4: 4 fr_poly_div_linear), same library and "
+                   "process, alternating call by call; traffic_ratio = "
+                   "(m + 1) / (3m - 1), the elements moved by one lincomb "
+                   "over those of the chain; gb_per_s counts (m + 1) n "
+                   "elements of 32 B",
+           "results": results}
+    text = json.dumps(doc, indent=1)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("log_sizes", nargs="*", type=int,
                     default=[16, 20, 22, 24])
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles",
-                                                  "opening_bench.json"))
+    ap.add_argument("--multiopen", action="store_true",
+                    help="time fr_lincomb, fr_poly_eval_batch and "
+                         "fr_poly_div_roots against the single calls they "
+                         "replace (default output "
+                         "profiles/multiopen_bench.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(
+            HERE, "profiles", "multiopen_bench.json" if args.multiopen
+            else "opening_bench.json")
+    if args.multiopen:
+        return main_multiopen(args)
     gpu = SpectreGpu([0])
     tile = ffi.fr_scan_tile_default()
     base = 1 << 16

@@ -75,7 +75,9 @@ int main() {
         for (uint64_t p = 1; p <= kMaxN; p *= 2) ns.push_back(p + 1);
         for (uint64_t n : ns) {
             if (n == 0 || n > kMaxN) continue;
-            for (uint32_t np : {1u, 3u, 8u}) check(n, tile, np);
+            // vectors per level: the points of fr_poly_eval, polynomials
+            // times points (up to 32 * 8) in fr_poly_eval_batch
+            for (uint32_t np : {1u, 3u, 8u, 15u, 256u}) check(n, tile, np);
         }
     }
     // a table that cannot hold the levels is reported, not overrun

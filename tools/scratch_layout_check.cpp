@@ -93,14 +93,22 @@ static void check_size(uint64_t n) {
         const PolyLevels dv = poly_levels(n, tile, tile, 0);
         const char* who = "poly levels";
         CHECK(ev.ok && dv.ok);
-        for (uint64_t npoints = 1; npoints <= 8; npoints++) {
-            Call c;
-            c.add<fp256>(npoints * ev.total);
-            check("poly eval", n, c);
+        // one partial vector per polynomial and point: fr_poly_eval has one
+        // polynomial, fr_poly_eval_batch up to 32
+        for (uint64_t npolys : {1ull, 2ull, 31ull, 32ull}) {
+            for (uint64_t npoints = 1; npoints <= 8; npoints++) {
+                Call c;
+                c.add<fp256>(npolys * npoints * ev.total);
+                check("poly eval", n, c);
+            }
         }
-        Call c;
-        c.add<fp256>(dv.total + 1);
-        check("poly div", n, c);
+        // a remainder slot per root: fr_poly_div_linear has one root,
+        // fr_poly_div_roots up to 8
+        for (uint64_t nroots = 1; nroots <= 8; nroots++) {
+            Call c;
+            c.add<fp256>(dv.total + nroots);
+            check("poly div", n, c);
+        }
     }
 }
 
