@@ -209,6 +209,12 @@ template <class C> FF_HD void ff_sub(fp256& o, const fp256& a, const fp256& b) {
     }
 }
 template <class C> FF_HD void ff_neg(fp256& o, const fp256& a) {
+    if constexpr (C::kChainAddSub) {  // 0 - a, branch-free like ff_sub
+        fp256 z;
+        ff_set_zero(z);
+        ff_sub<C>(o, z, a);
+        return;
+    }
     if (ff_is_zero(a)) { o = a; return; }
     fp256 m;
     for (int i = 0; i < 8; i++) m.l[i] = C::mod(i);
@@ -418,6 +424,65 @@ __device__ __forceinline__ void ff_sqr_cols(fp256& o, const fp256& A) {
     o.l[7] = (uint32_t)acc;
     ff_cond_sub_mod<C>(o, (uint32_t)(acc >> 32));
 }
+
+// ---- device sum of two products: one reduction for a*b + c*d ---------------
+// The column form with a second operand pair feeding each column: 128
+// operand products and 64 m*p products, where two multiplies pay 2*(64 + 64).
+// a*b + c*d < 2 m^2, so the value after the m_k products is below
+// m (2m / 2^256 + 1), which is below 2m (and below 2^255) while m < 2^255:
+// the one trial subtract is enough and the bytes are those of
+// ff_add(ff_mul(a, b), ff_mul(c, d)). A column takes at most 16 + 8 products.
+template <class C, int K>
+__device__ __forceinline__ void detail_ff_dot2_low_cols(
+    uint64_t& acc, uint32_t& ovf, const uint32_t* a, const uint32_t* b,
+    const uint32_t* c, const uint32_t* d, uint32_t* m) {
+    if constexpr (K < 8) {
+#pragma unroll
+        for (int i = 0; i <= K; i++) {
+            ff_mad64_(acc, ovf, a[i], b[K - i]);
+            ff_mad64_(acc, ovf, c[i], d[K - i]);
+        }
+#pragma unroll
+        for (int i = 0; i < K; i++) ff_mad64_s_(acc, ovf, m[i], C::mod(K - i));
+        m[K] = (uint32_t)acc * C::inv();
+        ff_mad64_s_(acc, ovf, m[K], C::mod(0));
+        acc = (acc >> 32) | ((uint64_t)ovf << 32);
+        ovf = 0;
+        detail_ff_dot2_low_cols<C, K + 1>(acc, ovf, a, b, c, d, m);
+    }
+}
+template <class C, int K>
+__device__ __forceinline__ void detail_ff_dot2_high_cols(
+    uint64_t& acc, uint32_t& ovf, const uint32_t* a, const uint32_t* b,
+    const uint32_t* c, const uint32_t* d, const uint32_t* m, uint32_t* out) {
+    if constexpr (K < 15) {
+#pragma unroll
+        for (int i = K - 7; i < 8; i++) {
+            ff_mad64_(acc, ovf, a[i], b[K - i]);
+            ff_mad64_(acc, ovf, c[i], d[K - i]);
+        }
+#pragma unroll
+        for (int i = K - 7; i < 8; i++) ff_mad64_s_(acc, ovf, m[i], C::mod(K - i));
+        out[K - 8] = (uint32_t)acc;
+        acc = (acc >> 32) | ((uint64_t)ovf << 32);
+        ovf = 0;
+        detail_ff_dot2_high_cols<C, K + 1>(acc, ovf, a, b, c, d, m, out);
+    }
+}
+template <class C>
+__device__ __forceinline__ void ff_dot2_cols(fp256& o, const fp256& A,
+                                             const fp256& B, const fp256& Cc,
+                                             const fp256& D) {
+    static_assert(C::mod(7) < 0x80000000u,
+                  "one trial subtract after a*b + c*d needs 2m <= 2^256");
+    uint32_t m[8];
+    uint64_t acc = 0;
+    uint32_t ovf = 0;
+    detail_ff_dot2_low_cols<C, 0>(acc, ovf, A.l, B.l, Cc.l, D.l, m);
+    detail_ff_dot2_high_cols<C, 8>(acc, ovf, A.l, B.l, Cc.l, D.l, m, o.l);
+    o.l[7] = (uint32_t)acc;
+    ff_cond_sub_mod<C>(o, (uint32_t)(acc >> 32));
+}
 #endif
 
 // The one multiply: the form the field names on the device, CIOS on the host.
@@ -441,6 +506,24 @@ template <class C> FF_HD void ff_sqr(fp256& o, const fp256& a) {
     }
 #endif
     ff_mul<C>(o, a, a);
+}
+
+// o = a*b + c*d (Montgomery), canonical: the bytes of
+// ff_add(ff_mul(a, b), ff_mul(c, d)) with one reduction where the field
+// multiplies with the asm column form. o may be any of the operands.
+template <class C>
+FF_HD void ff_dot2(fp256& o, const fp256& a, const fp256& b, const fp256& c,
+                   const fp256& d) {
+#if defined(FF_HAVE_ASM_MUL)
+    if constexpr (C::kAsmMul) {
+        ff_dot2_cols<C>(o, a, b, c, d);
+        return;
+    }
+#endif
+    fp256 t;
+    ff_mul<C>(t, a, b);
+    ff_mul<C>(o, c, d);
+    ff_add<C>(o, t, o);
 }
 
 // Montgomery conversion

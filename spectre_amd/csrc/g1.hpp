@@ -1,7 +1,12 @@
-// g1.hpp — BN254 G1 point arithmetic (Jacobian over Fq), host + device.
+// g1.hpp — BN254 G1 point arithmetic (Jacobian and XYZZ over Fq), host +
+// device.
 //
-// PRODUCT CODE. Formulas: EFD dbl-2009-l (a=0), madd-2007-bl, add-2007-bl
-// with explicit degenerate-case handling. Jacobian identity: Z == 0.
+// PRODUCT CODE. Jacobian formulas (the host fold and finish, the 96-byte
+// interface): EFD dbl-2009-l (a=0), madd-2007-bl, add-2007-bl with explicit
+// degenerate-case handling. Jacobian identity: Z == 0. The XYZZ forms below
+// them are what the MSM kernels add with. In the additions of both (and in
+// the XYZZ doubling), Y3 = r*(V - X3) - c*J is
+// one ff_dot2: two products under one Montgomery reduction.
 // Affine memory image = halo2curves G1Affine: x||y Montgomery Fq, 64 bytes,
 // identity encoded as (0, 0) (x=y=0 is not on y^2 = x^3 + 3).
 //
@@ -93,12 +98,11 @@ FF_HD void g1j_madd_ip(g1_jac& p, const g1_affine& q) {
     ff_sub<Fq>(H, H, J);
     ff_sub<Fq>(H, H, V);
     ff_sub<Fq>(H, H, V);
-    // Y3 = rr*(V - X3) - 2*Y1*J
+    // Y3 = rr*(V - X3) + (-2*Y1)*J, one reduction
     ff_sub<Fq>(V, V, H);
-    ff_mul<Fq>(V, rr, V);
-    ff_mul<Fq>(J, p.Y, J);
-    ff_add<Fq>(J, J, J);
-    ff_sub<Fq>(p.Y, V, J);
+    ff_add<Fq>(p.Y, p.Y, p.Y);
+    ff_neg<Fq>(p.Y, p.Y);
+    ff_dot2<Fq>(p.Y, rr, V, p.Y, J);
     p.X = H;
 }
 
@@ -138,20 +142,126 @@ FF_HD void g1j_add_ip(g1_jac& p, const g1_jac& q) {
     ff_sub<Fq>(H, H, J);
     ff_sub<Fq>(H, H, V);
     ff_sub<Fq>(H, H, V);
-    // Y3 = rr*(V - X3) - 2*S1*J
+    // Y3 = rr*(V - X3) + (-2*S1)*J, one reduction
     ff_sub<Fq>(V, V, H);
-    ff_mul<Fq>(V, rr, V);
-    ff_mul<Fq>(J, S1, J);
-    ff_add<Fq>(J, J, J);
-    ff_sub<Fq>(p.Y, V, J);
+    ff_add<Fq>(S1, S1, S1);
+    ff_neg<Fq>(S1, S1);
+    ff_dot2<Fq>(p.Y, rr, V, S1, J);
     p.X = H;
 }
 
-// MEASURED NEGATIVE (r2): XYZZ coordinates (mADD-2008-s, 8M + 2S against
-// madd-2007-bl's 7M + 4S) as the k_bucket_acc accumulator were SLOWER on
-// MI355X, bucket_acc 2.31 -> 3.09 ms at n=2^20, despite ~9% fewer multiplies;
-// the cause is not settled. The code is in git history, the numbers in
-// DESIGN.md.
+// ---- XYZZ: x = X/ZZ, y = Y/ZZZ, ZZ^3 == ZZZ^2; identity iff ZZ == 0 ---------
+// The coordinates of the MSM kernels from the bucket accumulator to the
+// window partials (msm.hip). EFD mADD-2008-s (8M + 2S), add-2008-s (12M + 2S)
+// and dbl-2008-s-1, with Y3 = R*(Q - X3) + (-c)*PPP through ff_dot2. The
+// degenerate cases are handled as in the Jacobian forms above.
+struct g1_xyzz {
+    fp256 X, Y, ZZ, ZZZ;
+};
+FF_HD void g1x_set_inf(g1_xyzz& p) {
+    ff_set_one<Fq>(p.X);
+    ff_set_one<Fq>(p.Y);
+    ff_set_zero(p.ZZ);
+    ff_set_zero(p.ZZZ);
+}
+FF_HD bool g1x_is_inf(const g1_xyzz& p) { return ff_is_zero(p.ZZ); }
+FF_HD void g1x_from_affine(g1_xyzz& o, const g1_affine& p) {
+    if (g1a_is_inf(p)) { g1x_set_inf(o); return; }
+    o.X = p.x;
+    o.Y = p.y;
+    ff_set_one<Fq>(o.ZZ);
+    ff_set_one<Fq>(o.ZZZ);
+}
+
+// p = 2p, dbl-2008-s-1, in place
+FF_HD void g1x_dbl_ip(g1_xyzz& p) {
+    if (g1x_is_inf(p)) return;
+    fp256 U, V, W, S, M;
+    ff_add<Fq>(U, p.Y, p.Y);
+    ff_sqr<Fq>(V, U);
+    ff_mul<Fq>(W, U, V);
+    ff_mul<Fq>(S, p.X, V);
+    ff_sqr<Fq>(M, p.X);
+    ff_add<Fq>(U, M, M);
+    ff_add<Fq>(M, U, M);
+    ff_mul<Fq>(p.ZZ, V, p.ZZ);
+    ff_mul<Fq>(p.ZZZ, W, p.ZZZ);
+    // X3 = M^2 - 2S
+    ff_sqr<Fq>(p.X, M);
+    ff_sub<Fq>(p.X, p.X, S);
+    ff_sub<Fq>(p.X, p.X, S);
+    // Y3 = M*(S - X3) + (-Y1)*W, one reduction
+    ff_sub<Fq>(S, S, p.X);
+    ff_neg<Fq>(p.Y, p.Y);
+    ff_dot2<Fq>(p.Y, M, S, p.Y, W);
+}
+
+// The part mADD and add share once U1, S1 (the accumulator's side) and
+// U2, S2 are known: P = U2 - U1, R = S2 - S1, then X3, Y3 and PP, PPP for the
+// caller's ZZ3, ZZZ3. False, with p already set, when P == 0.
+FF_HD bool g1x_add_core_(g1_xyzz& p, const fp256& U1, fp256& S1, fp256& U2,
+                         fp256& S2, fp256& PP, fp256& PPP) {
+    ff_sub<Fq>(U2, U2, U1);  // P
+    ff_sub<Fq>(S2, S2, S1);  // R
+    if (ff_is_zero(U2)) {
+        if (ff_is_zero(S2)) g1x_dbl_ip(p);
+        else g1x_set_inf(p);
+        return false;
+    }
+    fp256 Q;
+    ff_sqr<Fq>(PP, U2);
+    ff_mul<Fq>(PPP, U2, PP);
+    ff_mul<Fq>(Q, U1, PP);
+    // X3 = R^2 - PPP - 2Q
+    ff_sqr<Fq>(p.X, S2);
+    ff_sub<Fq>(p.X, p.X, PPP);
+    ff_sub<Fq>(p.X, p.X, Q);
+    ff_sub<Fq>(p.X, p.X, Q);
+    // Y3 = R*(Q - X3) + (-S1)*PPP, one reduction
+    ff_sub<Fq>(Q, Q, p.X);
+    ff_neg<Fq>(S1, S1);
+    ff_dot2<Fq>(p.Y, S2, Q, S1, PPP);
+    return true;
+}
+
+// p += q (q affine), mADD-2008-s, in place
+FF_HD void g1x_madd_ip(g1_xyzz& p, const g1_affine& q) {
+    if (g1a_is_inf(q)) return;
+    if (g1x_is_inf(p)) { g1x_from_affine(p, q); return; }
+    fp256 U1 = p.X, S1 = p.Y, U2, S2, PP, PPP;
+    ff_mul<Fq>(U2, q.x, p.ZZ);
+    ff_mul<Fq>(S2, q.y, p.ZZZ);
+    if (!g1x_add_core_(p, U1, S1, U2, S2, PP, PPP)) return;
+    ff_mul<Fq>(p.ZZ, p.ZZ, PP);
+    ff_mul<Fq>(p.ZZZ, p.ZZZ, PPP);
+}
+
+// p += q (both XYZZ), add-2008-s, in place
+FF_HD void g1x_add_ip(g1_xyzz& p, const g1_xyzz& q) {
+    if (g1x_is_inf(q)) return;
+    if (g1x_is_inf(p)) { p = q; return; }
+    fp256 U1, S1, U2, S2, PP, PPP;
+    ff_mul<Fq>(U1, p.X, q.ZZ);
+    ff_mul<Fq>(S1, p.Y, q.ZZZ);
+    ff_mul<Fq>(U2, q.X, p.ZZ);
+    ff_mul<Fq>(S2, q.Y, p.ZZZ);
+    if (!g1x_add_core_(p, U1, S1, U2, S2, PP, PPP)) return;
+    ff_mul<Fq>(p.ZZ, p.ZZ, q.ZZ);
+    ff_mul<Fq>(p.ZZ, p.ZZ, PP);
+    ff_mul<Fq>(p.ZZZ, p.ZZZ, q.ZZZ);
+    ff_mul<Fq>(p.ZZZ, p.ZZZ, PPP);
+}
+
+// (X*ZZ^2, Y*ZZZ^2, ZZZ): the same point in Jacobian form, 2M + 2S
+FF_HD void g1x_to_jac(g1_jac& o, const g1_xyzz& p) {
+    if (g1x_is_inf(p)) { g1j_set_inf(o); return; }
+    fp256 t;
+    ff_sqr<Fq>(t, p.ZZ);
+    ff_mul<Fq>(o.X, p.X, t);
+    ff_sqr<Fq>(t, p.ZZZ);
+    ff_mul<Fq>(o.Y, p.Y, t);
+    o.Z = p.ZZZ;
+}
 
 // host-side normalization (field inversion — used once per MSM result)
 FF_HD void g1j_to_affine(g1_affine& o, const g1_jac& p) {

@@ -118,13 +118,14 @@ struct MsmSlot {
     // boundary-run side arrays, one entry per accumulate thread
     // (ceil(ent / entries-per-thread)); grow together
     DevBuf<uint32_t> d_firstK, d_lastK;
-    DevBuf<g1_jac> d_firstP, d_lastP;
+    DevBuf<g1_xyzz> d_firstP, d_lastP;
     // grow together:
     DevBuf<uint32_t> d_offsets;  // nbt + 1 segment bounds
-    DevBuf<g1_jac> d_buckets;    // nbt
-    DevBuf<g1_jac> d_red;        // nbt/MSM_CHUNK weighted chunk sums W,
-                                 // as many plain chunk sums T, then three
-                                 // partials for each of nbatch * w_cnt windows
+    DevBuf<g1_xyzz> d_buckets;   // nbt
+    DevBuf<g1_xyzz> d_red;       // nbt/MSM_CHUNK weighted chunk sums W, then
+                                 // as many plain chunk sums T
+    DevBuf<g1_jac> d_part;       // three partials for each of nbatch * w_cnt
+                                 // windows, Jacobian like everything outward
     // The window partials (3 per window) come back through a PINNED per-slot
     // buffer: an async D2H into caller (pageable) memory silently blocks the
     // calling thread on ROCm, which serialized the whole slot pipeline in
@@ -137,7 +138,7 @@ struct MsmSlot {
     void release(hipStream_t shared) {
         release_all(d_keys_in, d_keys_out, d_vals_in, d_vals_out, d_sort_tmp,
                     d_firstK, d_lastK, d_firstP, d_lastP, d_offsets,
-                    d_buckets, d_red, h_wins);
+                    d_buckets, d_red, d_part, h_wins);
         if (stream && stream != shared) (void)hipStreamDestroy(stream);
         stream = nullptr;
     }

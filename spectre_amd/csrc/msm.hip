@@ -19,7 +19,7 @@
 //   3. k_bucket_offsets — binary-search segment bounds per bucket.
 //   4. k_bucket_acc     — equal-work partitioning: each thread owns exactly
 //                         E sorted entries, E chosen per call so small
-//                         inputs still fill the chip (serial Jacobian+affine
+//                         inputs still fill the chip (serial XYZZ+affine
 //                         mixed adds, entry stream prefetched through LDS);
 //                         interior runs write their bucket
 //                         exclusively, boundary runs are merged by
@@ -33,7 +33,10 @@
 //                         sum of the W_c, and the row and column sums of the
 //                         T_c (chunk index c = MSM_LO*hi + lo) weighted by
 //                         their 6-bit index; serial adds, then a pairwise
-//                         LDS tree.
+//                         LDS tree. Buckets, chunk sums and the tree are
+//                         XYZZ (g1.hpp); the thread that writes a partial
+//                         converts it to Jacobian, the format of everything
+//                         from here outward.
 // Host side: msm_slot_drain folds the three partials of each window,
 // P0 + CHUNK*(P1 + MSM_LO*P2) (9 doublings + 2 adds); ffi.cpp finishes each
 // batch with the window Horner (~255 doublings + adds) and one field
@@ -41,27 +44,27 @@
 //
 // All field math is 8x32-limb Montgomery (ff.hpp: the asm column multiply and
 // squaring, add/sub/reduce as carry chains) — VALU integer work, issue-bound:
-// in k_bucket_acc 2 057 of 6 229 vector instructions are v_mad_u64_u32 and as
+// in k_bucket_acc a third of the vector instructions are v_mad_u64_u32 and as
 // many their carry adds (field add/sub section); MFMA does not
 // apply to modular arithmetic.
 #include "internal.hpp"
 #include <hipcub/hipcub.hpp>
 
 #define THREADS 256
-// Point-arithmetic kernels hold a 24-VGPR Jacobian accumulator plus formula
+// Point-arithmetic kernels hold a 32-VGPR XYZZ accumulator plus formula
 // temporaries; at the default 4-waves/SIMD register budget (128 VGPR) hipcc
 // spills to scratch. Allowing 2 waves/SIMD (256 VGPR) removes the spills —
 // latency hiding comes from the serial-add structure, not occupancy
 // (measured: 1 add-chain/thread already saturates the VALU issue pipe).
-// With the carry-chain add/sub the kernels need 117-155 VGPRs (221 before)
+// With the carry-chain add/sub the kernels need 112-151 VGPRs (221 before)
 // and run at 3-4 waves/SIMD under the same bound
-// (profiles/field_chain_kernel_resources.txt).
+// (profiles/xyzz_kernel_resources.txt).
 #define PT_KERNEL __global__ __launch_bounds__(THREADS, 2)
 // The accumulate/fix kernels have no barriers (k_bucket_acc's LDS staging
 // is private to each wave, 8 KiB), so their block size only sets the
 // residency granule. MEASURED (r2): 64/128/256-thread blocks
 // are within run-to-run noise (acc 2.26-2.29 ms). The code object says
-// k_bucket_acc uses 111 VGPRs (4 waves/SIMD; four blocks stage 128 KiB of a
+// k_bucket_acc uses 112 VGPRs (4 waves/SIMD; four blocks stage 128 KiB of a
 // CU's 160 KiB of LDS). It had 165 (3 waves/SIMD) while ff_add / ff_sub were
 // 64-bit limb code behind branches — the profiler's VGPR column shows half
 // the allocation, which earlier notes misread as 4-5 waves/SIMD. One madd
@@ -187,11 +190,11 @@ ACC_KERNEL void k_bucket_acc(const uint32_t* __restrict__ off,
                             const uint32_t* __restrict__ vals,
                             const g1_affine* __restrict__ bases,
                             uint32_t nb_total, uint32_t E,
-                            g1_jac* __restrict__ buckets,
+                            g1_xyzz* __restrict__ buckets,
                             uint32_t* __restrict__ firstK,
-                            g1_jac* __restrict__ firstP,
+                            g1_xyzz* __restrict__ firstP,
                             uint32_t* __restrict__ lastK,
-                            g1_jac* __restrict__ lastP) {
+                            g1_xyzz* __restrict__ lastP) {
     // [wave][slot][lane]: slots 0-3 point x|y, 4-5 key quads, 6-7 value quads
     __shared__ uint4 stage[ACC_WAVES][8][64];
     const uint32_t ent = off[nb_total];  // real (non-skip) entries
@@ -213,12 +216,15 @@ ACC_KERNEL void k_bucket_acc(const uint32_t* __restrict__ off,
         const uint4* src = (const uint4*)(bases + (st[6][lane].x & 0x7fffffffu));
         for (int c = 0; c < 4; c++) glds16(src + c, st[c]);
     }
-    // MEASURED NEGATIVE RESULT (r2): accumulating runs in XYZZ
-    // (mADD-2008-s, 8M+2S — see g1.hpp) with a per-run Jacobian conversion
-    // is bit-exact but SLOWER (bucket_acc 2.31 -> 3.09 ms at n=2^20): the
-    // fewer multiplies do not pay for the larger accumulator.
-    g1_jac acc;
-    g1j_set_inf(acc);
+    // XYZZ (mADD-2008-s, 8M + 2S with Y3's two products under one
+    // reduction), stored as it is: the flush below is a plain store. An
+    // earlier XYZZ accumulator converted every finished run to Jacobian in
+    // that branch (6M + 2S, issued by the whole wave whenever one lane ends a
+    // run, about 87 % of iterations) and measured 2.31 -> 3.09 ms; without
+    // the conversion this one is 9 % faster than the Jacobian madd
+    // (XYZZ section).
+    g1_xyzz acc;
+    g1x_set_inf(acc);
     bool first = true;
     for (uint32_t i = 0; i < cnt; i++) {
         glds_landed();  // point i; quad issued at the previous multiple of 4
@@ -254,11 +260,11 @@ ACC_KERNEL void k_bucket_acc(const uint32_t* __restrict__ off,
             } else {
                 buckets[k] = acc;  // interior run: exclusive writer
             }
-            g1j_set_inf(acc);
+            g1x_set_inf(acc);
             k = kj;
         }
         if (v & 0x80000000u) ff_neg<Fq>(p.y, p.y);
-        g1j_madd_ip(acc, p);
+        g1x_madd_ip(acc, p);
     }
     if (first) {  // whole range is one run
         firstK[t] = k;
@@ -270,20 +276,40 @@ ACC_KERNEL void k_bucket_acc(const uint32_t* __restrict__ off,
     }
 }
 
+// A point operand read whole, 16 bytes at a time, into registers before the
+// add that consumes it. Handed a reference into memory, the inlined add loads
+// each limb where a product first needs it and again at every later use, one
+// dword and one wait at a time (the code object of k_window_chunks had 147
+// global loads for its one 32-limb operand): in the fix, chunk and tail
+// kernels, which run at one or two waves per SIMD, that latency is not hidden.
+// The empty asm pins every limb in a VGPR, so the loads cannot sink.
+__device__ __forceinline__ g1_xyzz pt_load(const g1_xyzz* src) {
+    static_assert(sizeof(g1_xyzz) == 8 * sizeof(uint4), "four 32-byte elements");
+    uint4 q[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) q[i] = ((const uint4*)src)[i];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        asm volatile("" : "+v"(q[i].x), "+v"(q[i].y), "+v"(q[i].z), "+v"(q[i].w));
+    g1_xyzz v;
+    memcpy(&v, q, sizeof v);
+    return v;
+}
+
 // merge boundary partials: bucket b's segment [s,e) spans threads ts..te;
 // interior-only buckets were already written by their exclusive thread.
 ACC_KERNEL void k_bucket_fix(const uint32_t* __restrict__ off,
                             const uint32_t* __restrict__ firstK,
-                            const g1_jac* __restrict__ firstP,
+                            const g1_xyzz* __restrict__ firstP,
                             const uint32_t* __restrict__ lastK,
-                            const g1_jac* __restrict__ lastP,
+                            const g1_xyzz* __restrict__ lastP,
                             uint32_t nb_total, uint32_t E,
-                            g1_jac* __restrict__ buckets) {
+                            g1_xyzz* __restrict__ buckets) {
     uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb_total) return;
     uint32_t s = off[b], e = off[b + 1];
     if (s == e) {
-        g1j_set_inf(buckets[b]);
+        g1x_set_inf(buckets[b]);
         return;
     }
     uint32_t ts = s / E, te = (e - 1) / E;
@@ -294,11 +320,11 @@ ACC_KERNEL void k_bucket_fix(const uint32_t* __restrict__ off,
     const uint32_t ent = off[nb_total];
     if (ts == te && (s % E) && (e % E) && e != ent)
         return;
-    g1_jac acc;
-    g1j_set_inf(acc);
+    g1_xyzz acc;
+    g1x_set_inf(acc);
     for (uint32_t t = ts; t <= te; t++) {  // ascending = sorted entry order
-        if (firstK[t] == b) g1j_add_ip(acc, firstP[t]);
-        if (lastK[t] == b) g1j_add_ip(acc, lastP[t]);
+        if (firstK[t] == b) g1x_add_ip(acc, pt_load(firstP + t));
+        if (lastK[t] == b) g1x_add_ip(acc, pt_load(lastP + t));
     }
     buckets[b] = acc;
 }
@@ -312,19 +338,19 @@ ACC_KERNEL void k_bucket_fix(const uint32_t* __restrict__ off,
 // c*CHUNK per chunk was half of this kernel's adds; kernel 6 applies the
 // offsets to 2*64 marginal sums per window instead. Uniform in the flattened
 // (batch*NWIN + w) window index, so batching needs no changes here.
-PT_KERNEL void k_window_chunks(const g1_jac* __restrict__ buckets,
+PT_KERNEL void k_window_chunks(const g1_xyzz* __restrict__ buckets,
                                uint32_t total_chunks,
-                               g1_jac* __restrict__ outW,
-                               g1_jac* __restrict__ outT) {
+                               g1_xyzz* __restrict__ outW,
+                               g1_xyzz* __restrict__ outT) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total_chunks) return;
-    const g1_jac* B = buckets + (uint64_t)t * MSM_CHUNK;
-    g1_jac accT, accW;
-    g1j_set_inf(accT);
-    g1j_set_inf(accW);
+    const g1_xyzz* B = buckets + (uint64_t)t * MSM_CHUNK;
+    g1_xyzz accT, accW;
+    g1x_set_inf(accT);
+    g1x_set_inf(accW);
     for (int j = MSM_CHUNK - 1; j >= 0; j--) {
-        g1j_add_ip(accT, B[j]);
-        g1j_add_ip(accW, accT);
+        g1x_add_ip(accT, pt_load(B + j));
+        g1x_add_ip(accW, accT);
     }
     outW[t] = accW;
     outT[t] = accT;
@@ -353,8 +379,8 @@ PT_KERNEL void k_window_chunks(const g1_jac* __restrict__ buckets,
 // takes the stage from 0.74 to 0.61 ms at every n and one synchronous call
 // at n = 2^12 from 1.42 to 1.31 ms; the pipelined throughput at n = 2^20 is
 // the same within its noise. 512 threads is two waves on each SIMD of a CU,
-// within the 256-VGPR budget (the kernel has 143 VGPRs, 220 before the
-// carry-chain add/sub).
+// within the 256-VGPR budget (the kernel has 140 VGPRs, 220 before the
+// carry-chain add/sub). The tree's XYZZ elements take 32 KiB of LDS.
 #ifndef WSUM_THREADS
 #define WSUM_THREADS 512
 #endif
@@ -364,15 +390,15 @@ static_assert(WSUM_THREADS % MSM_LO == 0 && MSM_HI % (WSUM_THREADS / MSM_LO) == 
 static_assert(MSM_HI <= WSUM_THREADS && WSUM_THREADS % MSM_HI == 0 &&
               MSM_LO % (WSUM_THREADS / MSM_HI) == 0, "row shares");
 __global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_tail(
-    const g1_jac* __restrict__ inW, const g1_jac* __restrict__ inT,
+    const g1_xyzz* __restrict__ inW, const g1_xyzz* __restrict__ inT,
     g1_jac* __restrict__ out) {
-    __shared__ g1_jac lds[WSUM_THREADS / 2];
+    __shared__ __align__(16) g1_xyzz lds[WSUM_THREADS / 2];  // pt_load: 16 B
     const uint32_t w = blockIdx.x / 3, role = blockIdx.x % 3;
     const uint32_t t = threadIdx.x;
     // marginals of this role, and this thread's share: cnt elements from
     // src, stride apart
     const uint32_t M = role == 0 ? 0 : role == 1 ? MSM_LO : MSM_HI;
-    const g1_jac* src;
+    const g1_xyzz* src;
     uint32_t stride, cnt;
     if (role == 0) {
         src = inW + (uint64_t)w * MSM_CPW + t;
@@ -389,28 +415,30 @@ __global__ __launch_bounds__(WSUM_THREADS, 2) void k_window_tail(
               (t / MSM_HI) * cnt;
         stride = 1;
     }
-    g1_jac acc;
-    g1j_set_inf(acc);
-    for (uint32_t j = 0; j < cnt; j++) g1j_add_ip(acc, src[(uint64_t)j * stride]);
+    g1_xyzz acc;
+    g1x_set_inf(acc);
+    for (uint32_t j = 0; j < cnt; j++)
+        g1x_add_ip(acc, pt_load(src + (uint64_t)j * stride));
     for (uint32_t k = WSUM_THREADS / 2; k >= 1; k >>= 1) {
         if (2 * k == M && t < M) {  // acc = marginal t: acc *= t
-            if (t == 0) g1j_set_inf(acc);
-            if (!g1j_is_inf(acc)) {
-                g1_jac r;
-                g1j_set_inf(r);
+            if (t == 0) g1x_set_inf(acc);
+            if (!g1x_is_inf(acc)) {
+                g1_xyzz r;
+                g1x_set_inf(r);
                 for (uint32_t bit = M >> 1; bit; bit >>= 1) {
-                    g1j_dbl_ip(r);
-                    if (t & bit) g1j_add_ip(r, acc);
+                    g1x_dbl_ip(r);
+                    if (t & bit) g1x_add_ip(r, acc);
                 }
                 acc = r;
             }
         }
         if (t >= k && t < 2 * k) lds[t - k] = acc;
         __syncthreads();
-        if (t < k) g1j_add_ip(acc, lds[t]);
+        if (t < k) g1x_add_ip(acc, pt_load(lds + t));
         __syncthreads();
     }
-    if (t == 0) out[blockIdx.x] = acc;
+    // the one conversion: the partials leave in the 96-byte Jacobian format
+    if (t == 0) g1x_to_jac(out[blockIdx.x], acc);
 }
 
 // ---- host orchestration ---------------------------------------------------
@@ -478,7 +506,8 @@ static int ensure_msm_scratch(MsmSlot& ds, uint64_t ent, uint32_t nwin,
     RC_TRY(ds.d_lastP.reserve(nt));
     RC_TRY(ds.d_offsets.reserve(nbt + 1));
     RC_TRY(ds.d_buckets.reserve(nbt));
-    RC_TRY(ds.d_red.reserve(2 * nbt / MSM_CHUNK + 3 * (uint64_t)nwin));
+    RC_TRY(ds.d_red.reserve(2 * nbt / MSM_CHUNK));
+    RC_TRY(ds.d_part.reserve(3 * (uint64_t)nwin));
     size_t sort_need = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(
         nullptr, sort_need, ds.d_keys_in.ptr, ds.d_keys_out.ptr,
@@ -622,9 +651,9 @@ static int msm_enqueue(spectre_gpu_ctx* ctx, DeviceState& dstate, MsmSlot& ds,
                        ds.d_lastP.ptr, nbt, acc_e, ds.d_buckets.ptr);
     timer.stamp(4);
     const uint32_t nchunks = nbt / MSM_CHUNK;
-    g1_jac* redW = ds.d_red.ptr;
-    g1_jac* redT = redW + nchunks;
-    g1_jac* redP = redT + nchunks;  // 3 partials per window
+    g1_xyzz* redW = ds.d_red.ptr;
+    g1_xyzz* redT = redW + nchunks;
+    g1_jac* redP = ds.d_part.ptr;  // 3 partials per window
     hipLaunchKernelGGL(k_window_chunks,
                        dim3((nchunks + THREADS - 1) / THREADS), dim3(THREADS),
                        0, st, ds.d_buckets.ptr, nchunks, redW, redT);
