@@ -585,6 +585,18 @@ def test_ntt_three_pass_forced_vs_oracle(oracle, golden):
                                  FORCE3_LOG_NS)
 
 
+# a second forced item (test_ntt_split.py reads this list too)
+FORCE3_LARGE_LOG_NS = (21, 22)
+
+
+def test_ntt_three_pass_forced_large_vs_oracle(oracle, golden):
+    """Forced three passes at log_n 21 and 22, splits (7,7,7) and (8,7,7):
+    the (7,7,middle), (7,0,last) and (8,7,middle) passes that 2^26 and 2^27
+    end with, against the oracle itself on all four legs."""
+    _ntt_legs_vs_oracle_in_child({"SPECTRE_NTT_FORCE3": "1"},
+                                 FORCE3_LARGE_LOG_NS)
+
+
 def test_ntt_two_pass_short_first_axis_vs_oracle(oracle, golden):
     """The default rule's (1,12) and (2,12) splits at log_n 13 and 14: a
     one- and a two-entry twiddle table on the strided pass, all four legs."""
@@ -603,8 +615,16 @@ def test_ntt_2pow25_roundtrip(gpu, oracle, golden):
     for _ in range(28 - log_n):
         w = oracle.fr_mul(w, w)
     wi = oracle.fr_inv(w)
+    # copies of one chunk, each rotated by another odd element count, as
+    # test_ntt_shapes_gpu.vec() builds them: plainly repeated, the vector has
+    # period 2^20 and its DFT is zero at 31 outputs of 32, where no wrong
+    # factor shows
     chunk = oracle.gen_fr_vector(1 << 20, 2525)
-    a = chunk * (n >> 20)
+    parts = []
+    for j in range(n >> 20):
+        cut = 32 * ((j * 40503) % (1 << 20))
+        parts.append(chunk[cut:] + chunk[:cut])
+    a = b"".join(parts)
     d = gpu.malloc(32 * n)
     gpu.upload(d, a)
     gpu.ntt_device(d, log_n, w)

@@ -14,21 +14,24 @@ import pytest
 import test_gpu_parity
 import test_ntt_extend_gpu
 import test_ntt_shapes_gpu
+import test_ntt_three_axis_gpu
 from spectre_amd import ffi
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the default rule as ntt.hip's comments state the measured choices:
 # one pass up to 2^12; k[1] = 12 up to 2^20, balanced above; three balanced
-# axes at 2^25; k[0] = 12 from 2^26
+# axes at 2^25; k[0] = 12 from 2^26, the rest balanced
 TABLE = {log_n: (log_n,) for log_n in range(1, 13)}
 TABLE.update({log_n: (log_n - 12, 12) for log_n in range(13, 21)})
 TABLE.update({21: (10, 11), 22: (11, 11), 23: (11, 12), 24: (12, 12),
-              25: (9, 8, 8)})
+              25: (9, 8, 8), 26: (12, 7, 7), 27: (12, 8, 7), 28: (12, 8, 8)})
+THREE_AXIS = range(25, 29)
 # the sizes the forced three-pass tests run, and the splits their docstrings
 # name
-FORCE3_SIZES = (3, 4, 5, 6, 7, 10, 12, 14)
-FORCE3_TABLE = {3: (1, 1, 1), 4: (2, 1, 1), 5: (2, 2, 1), 7: (3, 2, 2)}
+FORCE3_SIZES = (3, 4, 5, 6, 7, 10, 12, 14, 21, 22)
+FORCE3_TABLE = {3: (1, 1, 1), 4: (2, 1, 1), 5: (2, 2, 1), 7: (3, 2, 2),
+                21: (7, 7, 7), 22: (8, 7, 7)}
 
 
 def classes(split):
@@ -81,8 +84,7 @@ def test_out_of_range_is_zero_passes():
 def test_default_table():
     for log_n, split in TABLE.items():
         assert ffi.ntt_split(log_n) == split, log_n
-    for log_n in (26, 27, 28):
-        assert ffi.ntt_split(log_n)[0] == 12, log_n
+    assert set(TABLE) == set(range(1, 29))
 
 
 def test_forced_table():
@@ -118,6 +120,45 @@ def test_coverage_check_sees_a_missing_shape():
         assert gone in {log_n for log_n, _ in uncovered(required, reached)}, gone
 
 
+def three_axis_reached(sizes):
+    """The classes test_ntt_three_axis_gpu runs with `sizes` as its size
+    list. The extend cases' first pass is the EXT instantiation, other code,
+    so only their later passes count."""
+    reached = [classes(ffi.ntt_split(s)) for s in sizes]
+    reached += [classes(ffi.ntt_split(log_n + ext))[1:]
+                for log_n, ext in test_ntt_three_axis_gpu.EXTEND]
+    return reached
+
+
+def test_three_axis_list_covers_25_to_28():
+    """Every class of pass at log_n 25..28 is one that a size of
+    test_ntt_three_axis_gpu.SIZES runs, its extend cases reach the same
+    sizes, and the sub-transform its reference rests on is a size that
+    test_ntt_shapes_gpu compares with the oracle."""
+    required = {log_n: ffi.ntt_split(log_n) for log_n in THREE_AXIS}
+    assert all(len(split) == 3 for split in required.values())
+    reached = three_axis_reached(test_ntt_three_axis_gpu.SIZES)
+    missing = uncovered(required, reached)
+    assert not missing, f"(log_n, class) no size reaches: {missing}"
+    assert {c for s in reached for c in s} == {
+        c for split in required.values() for c in classes(split)}
+    assert {log_n + ext for log_n, ext in test_ntt_three_axis_gpu.EXTEND} == set(
+        THREE_AXIS)
+    assert test_ntt_three_axis_gpu.SUB_LOG in test_ntt_shapes_gpu.LARGE
+    assert (test_ntt_three_axis_gpu.MACHINERY_LOG - 2
+            in test_ntt_shapes_gpu.FULL)
+
+
+def test_three_axis_check_sees_a_missing_size():
+    """The check above fails for each single log_n taken out of SIZES: the
+    first pass of every size is a class of its own."""
+    required = {log_n: ffi.ntt_split(log_n) for log_n in THREE_AXIS}
+    for gone in THREE_AXIS:
+        reached = three_axis_reached(
+            s for s in test_ntt_three_axis_gpu.SIZES if s != gone)
+        assert gone in {log_n for log_n, _ in uncovered(required, reached)}, gone
+
+
 def test_forced_lists_cover_the_forced_rule():
     """Every class of pass the three-axis rule has at FORCE3_SIZES is one the
     forced tests run. The extend test's first pass is the EXT instantiation,
@@ -125,7 +166,8 @@ def test_forced_lists_cover_the_forced_rule():
     required = {log_n: ffi.ntt_split(log_n, force3=True)
                 for log_n in FORCE3_SIZES}
     reached = [classes(ffi.ntt_split(s, force3=True))
-               for s in test_gpu_parity.FORCE3_LOG_NS]
+               for s in (test_gpu_parity.FORCE3_LOG_NS
+                         + test_gpu_parity.FORCE3_LARGE_LOG_NS)]
     reached += [classes(ffi.ntt_split(log_n + ext, force3=True))[1:]
                 for log_n, ext in test_ntt_extend_gpu.FORCE3]
     missing = uncovered(required, reached)
