@@ -78,7 +78,9 @@ int spectre_gpu_msm_g1(spectre_gpu_ctx*, uint64_t bases_id,
 /* Batched MSM: `nbatch` scalar vectors (batch-major, nbatch*n*32 B) over ONE
  * shared base set — the shape of create_proof's back-to-back column commits
  * (same SRS); one fused sort/accumulate pass, bases stay cache-resident
- * across the batch. out_affine receives nbatch results (64 B each). */
+ * across the batch. out_affine receives nbatch results (64 B each).
+ * nbatch outside 1..SPECTRE_MSM_MAX_BATCH is refused with -3 before anything
+ * is sized by it, n == 0 included. */
 int spectre_gpu_msm_g1_batch(spectre_gpu_ctx*, uint64_t bases_id,
                              const uint8_t* bases /* n*64B */,
                              const uint8_t* scalars /* nbatch*n*32B */,
@@ -221,9 +223,15 @@ int spectre_gpu_ntt_fr_extend_device(spectre_gpu_ctx*, int dev,
 /* ---- pointwise Fr vector ops (device buffers, Montgomery form) ----------
  * The quotient phase evaluates gate expressions pointwise between the
  * iFFT and coset-FFT passes; these ops let a patched evaluator keep
- * polynomials device-resident. out may alias a or b.
+ * polynomials device-resident. out may alias a or b, and
+ * a may alias b, where "alias" means the SAME pointer: a lane reads element
+ * i of its inputs before it writes element i and touches no other. Buffers
+ * that overlap without being equal are not supported (and not checked).
  *   op 0: out = a + b        op 1: out = a - b       op 2: out = a * b
  *   op 3: out = a * c        op 4: out = a + c * b   (c = one Fr element)
+ * Refused with -1: op outside 0..4, NULL d_a or d_out, NULL d_b for ops
+ * 0, 1, 2 and 4, NULL c for ops 3 and 4. n == 0: nothing is done and 0 is
+ * returned. Synchronizes.
  */
 /* ---- gate-expression evaluator (quotient phase) -------------------------
  * Evaluates one custom-gate expression over every row of a (usually
@@ -241,7 +249,19 @@ int spectre_gpu_ntt_fr_extend_device(spectre_gpu_ctx*, int dev,
  *   y == NULL : out[row]  = result               (first gate)
  *   y != NULL : out[row] = out[row]*y + result   (halo2's h = h*y + gate)
  * d_cols is a HOST array of ncols DEVICE pointers; constants/program/y are
- * host pointers. */
+ * host pointers. n is a nonzero power of two.
+ *
+ * Refused before anything is launched, and then nothing is written:
+ *   -1  a NULL d_cols, program or d_out, nops == 0, NULL constants with
+ *       nconst != 0; a NULL entry in d_cols, whether or not the program
+ *       reads that column; any byte shared between d_out[0..n) and any
+ *       d_cols[j][0..n), equal pointers included (a lane reads rotated rows
+ *       that other lanes write, so no overlap has a defined result);
+ *   -3  n zero or not a power of two; a malformed program (unknown opcode,
+ *       column index >= ncols, constant index >= nconst, an operator on too
+ *       short a stack, depth above SPECTRE_GATE_MAX_DEPTH, a final stack of
+ *       other than one value); a rotation with |b * rot_scale| >= n, the
+ *       product taken in 64 bits (rot_scale == 0 makes every rotation 0). */
 #define SPECTRE_GATE_OP_COL 0
 #define SPECTRE_GATE_OP_CONST 1
 #define SPECTRE_GATE_OP_ADD 2

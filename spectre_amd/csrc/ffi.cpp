@@ -189,6 +189,17 @@ static int check_dev(spectre_gpu_ctx* ctx, int dev) {
     return 0;
 }
 
+// A batched MSM sizes host memory by nbatch, so the bound that the MSM itself
+// applies (msm_acquire_slot) is checked before anything is sized.
+static int check_nbatch(uint32_t nbatch) {
+    if (nbatch == 0 || nbatch > SPECTRE_MSM_MAX_BATCH) {
+        set_err("msm: nbatch %u out of range [1,%d]", nbatch,
+                SPECTRE_MSM_MAX_BATCH);
+        return -3;
+    }
+    return 0;
+}
+
 // do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
 static bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b,
                            uint64_t b_bytes) {
@@ -359,6 +370,7 @@ int spectre_gpu_msm_g1_batch_device(spectre_gpu_ctx* ctx, int dev,
                                     uint64_t n, uint32_t flags,
                                     uint8_t* out_affine) {
     if (check_dev(ctx, dev)) return -1;
+    if (check_nbatch(nbatch)) return -3;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     std::vector<g1_jac> wins((size_t)nbatch * MSM_NWIN);
     RC_TRY(msm_device(ctx, dev, msm_call(d_bases, d_scalars, nbatch, n, flags),
@@ -418,6 +430,7 @@ int spectre_gpu_msm_g1_batch(spectre_gpu_ctx* ctx, uint64_t bases_id,
         set_err("null ctx");
         return -1;
     }
+    if (check_nbatch(nbatch)) return -3;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (n == 0) {
         memset(out_affine, 0, (size_t)64 * nbatch);
@@ -577,6 +590,18 @@ int spectre_gpu_fr_gate_eval(spectre_gpu_ctx* ctx, int dev,
     if (!d_cols || !program || !nops || !d_out || (nconst && !constants)) {
         set_err("gate_eval: bad arguments");
         return -1;
+    }
+    // every column, read by the program or not, is a buffer clear of d_out:
+    // with a rotation a lane reads rows that other lanes write
+    for (uint32_t j = 0; j < ncols; j++) {
+        if (!d_cols[j]) {
+            set_err("gate_eval: null device pointer in d_cols[%u]", j);
+            return -1;
+        }
+        if (ranges_overlap(d_cols[j], 32 * n, d_out, 32 * n)) {
+            set_err("gate_eval: d_out overlaps d_cols[%u]", j);
+            return -1;
+        }
     }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     fp256 yv;

@@ -192,6 +192,7 @@ int fr_vec_op_device(spectre_gpu_ctx* ctx, int dev, int op, const fp256* d_a,
                      uint64_t n) {
     DeviceState& ds = ctx->devs[dev];
     HIP_TRY(hipSetDevice(ds.device_id));
+    if (n == 0) return 0;
     fp256 cv;
     ff_set_zero(cv);
     if (c) cv = *c;

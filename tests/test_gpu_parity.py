@@ -521,6 +521,20 @@ def test_error_paths(gpu):
         gpu.ntt(b"\x00" * 32, 29, b"\x01" + b"\x00" * 31)
     with _pytest.raises(RuntimeError, match="nbatch"):
         gpu.msm_batch(b"\x00" * 64, b"\x00" * (33 * 32), 33, 1)
+    # the batch bound holds before anything is sized by nbatch: with n = 0,
+    # and on the device-pointer entry (refused before a pointer is read)
+    with pytest.raises(RuntimeError, match="rc=-3: .*nbatch 33"):
+        gpu.msm_batch(None, b"", 33, 0)
+    d_b, d_s = gpu.malloc(64), gpu.malloc(33 * 32)
+    try:
+        for nbatch in (0, 33):
+            with pytest.raises(RuntimeError,
+                               match=f"rc=-3: .*nbatch {nbatch}"):
+                gpu.msm_batch_device(d_b, d_s, nbatch, 1)
+    finally:
+        gpu.free(d_b)
+        gpu.free(d_s)
+    assert gpu.msm_batch(None, b"", 32, 0) == [bytes(64)] * 32
 
 
 def _ntt_legs_vs_oracle_in_child(env, log_ns):
@@ -637,32 +651,17 @@ def test_ntt_2pow25_roundtrip(gpu, oracle, golden):
     gpu.free(d)
 
 
-def _ref_gate_eval(cols_int, consts_int, program, n, rot_scale, r_mod,
-                   y_int=None, prev=None):
-    """Bigint restatement of the gate-expression evaluator semantics
-    (the checker for SURVEY §8f-3): stack machine per row, rotations
-    (row + rot*rot_scale) mod n, out = prev*y + v when y given."""
-    out = []
-    for row in range(n):
-        st = []
-        for op, a, b in program:
-            if op == 0:
-                st.append(cols_int[a][(row + b * rot_scale) % n])
-            elif op == 1:
-                st.append(consts_int[a])
-            elif op == 5:
-                st[-1] = (-st[-1]) % r_mod
-            else:
-                rhs = st.pop()
-                lhs = st.pop()
-                st.append((lhs + rhs) % r_mod if op == 2 else
-                          (lhs - rhs) % r_mod if op == 3 else
-                          lhs * rhs % r_mod)
-        v = st[0]
-        if y_int is not None:
-            v = (prev[row] * y_int + v) % r_mod
-        out.append(v)
-    return out
+def _gate_ref():
+    """tests/gate_ref.py, the bigint restatement of the gate-expression
+    evaluator (the checker for SURVEY §8f-3), loaded by path."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "gate_ref", os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                 "gate_ref.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 def test_gate_eval_vs_reference(gpu, oracle):
@@ -671,6 +670,8 @@ def test_gate_eval_vs_reference(gpu, oracle):
     column, plus random programs, vs the bigint restatement."""
     import random
     R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+    gate_ref = _gate_ref()
+    assert gate_ref.R == R
     n = 1 << 10
     rng = random.Random(8015)
 
@@ -701,7 +702,7 @@ def test_gate_eval_vs_reference(gpu, oracle):
             (G.GATE_COL, 1, 3), (G.GATE_SUB, 0, 0),
             (G.GATE_MUL, 0, 0)]
     G.gate_eval(d_cols, b"", flex, n, rot_scale=4, d_out=d_out)
-    want = _ref_gate_eval(cols_int, [], flex, n, 4, R)
+    want = gate_ref.eval_program(cols_int, [], flex, n, 4)
     assert to_ints(bytes(G.download(d_out, 32 * n))) == want
 
     # accumulate form out = out*y + v, with constants and negation
@@ -711,30 +712,17 @@ def test_gate_eval_vs_reference(gpu, oracle):
              (G.GATE_CONST, 1, 0), (G.GATE_NEG, 0, 0), (G.GATE_ADD, 0, 0)]
     G.gate_eval(d_cols, fr_vec(consts), prog2, n, rot_scale=1,
                 y=fr_vec([y]), d_out=d_out)
-    want2 = _ref_gate_eval(cols_int, consts, prog2, n, 1, R, y, want)
+    want2 = gate_ref.eval_program(cols_int, consts, prog2, n, 1, y, want)
     assert to_ints(bytes(G.download(d_out, 32 * n))) == want2
 
-    # random well-formed programs to max depth
-    for trial in range(6):
-        prog, depth, maxd = [], 0, 0
+    # random well-formed programs of a set depth, the maximum included
+    for trial, depth in enumerate((8, 8, 7, 6, 4, 2)):
         consts = [rng.randrange(R) for _ in range(3)]
-        while len(prog) < 20 or depth != 1:
-            if depth >= 2 and (depth >= 7 or rng.random() < 0.5):
-                prog.append((rng.choice([G.GATE_ADD, G.GATE_SUB, G.GATE_MUL]),
-                             0, 0))
-                depth -= 1
-            elif depth >= 1 and rng.random() < 0.1:
-                prog.append((G.GATE_NEG, 0, 0))
-            elif rng.random() < 0.7:
-                prog.append((G.GATE_COL, rng.randrange(ncols),
-                             rng.randrange(-3, 4)))
-                depth += 1
-            else:
-                prog.append((G.GATE_CONST, rng.randrange(3), 0))
-                depth += 1
-            maxd = max(maxd, depth)
+        prog, maxd = gate_ref.compile_tree(gate_ref.random_tree(
+            rng, ncols, 3, range(-3, 4), depth))
+        assert maxd == depth
         G.gate_eval(d_cols, fr_vec(consts), prog, n, rot_scale=2, d_out=d_out)
-        want = _ref_gate_eval(cols_int, consts, prog, n, 2, R)
+        want = gate_ref.eval_program(cols_int, consts, prog, n, 2)
         assert to_ints(bytes(G.download(d_out, 32 * n))) == want, trial
 
     # validation: malformed programs are rejected loudly
@@ -799,7 +787,7 @@ def test_quotient_pipeline_device_resident(gpu, oracle):
             oracle.fr_to_canonical(raw[32 * i:32 * (i + 1)]), "little")
             for i in range(n)]
     ci = [to_ints(c) for c in ref_cosets]
-    ev = _ref_gate_eval(ci, [], flex, n, 4, R)
+    ev = _gate_ref().eval_program(ci, [], flex, n, 4)
     ev_bytes = b"".join(
         oracle.fr_from_canonical(v.to_bytes(32, "little")) for v in ev)
     want = oracle.ntt(ev_bytes, log_n, wi, inverse=True, coset_gen=g5i)

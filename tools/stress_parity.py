@@ -3,6 +3,7 @@
 configurations against the CPU oracle, bit-exact, plus run-to-run and
 shard-count determinism. Seeded; prints a summary line. Not part of the
 pytest suite (runtime ~minutes) — run ad hoc to deepen parity evidence."""
+import importlib.util
 import os
 import random
 import sys
@@ -13,6 +14,12 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "oracle"))
 import pywrap as oracle  # noqa: E402
 from spectre_amd import SpectreGpu, ffi  # noqa: E402
+
+# the gate generator and its bigint evaluator are the test suite's
+_spec = importlib.util.spec_from_file_location(
+    "gate_ref", os.path.join(HERE, "tests", "gate_ref.py"))
+gate_ref = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gate_ref)
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
@@ -102,24 +109,11 @@ def main():
                         for _ in range(ncols)]
             consts = [rng.randrange(R) for _ in range(2)]
             rot_scale = rng.choice([1, 2, 4])
-            prog, depth = [], 0
-            while len(prog) < rng.randrange(3, 24) or depth != 1:
-                if depth >= 2 and (depth >= 7 or rng.random() < 0.5):
-                    prog.append((rng.choice([gpu.GATE_ADD, gpu.GATE_SUB,
-                                             gpu.GATE_MUL]), 0, 0))
-                    depth -= 1
-                elif depth >= 1 and rng.random() < 0.1:
-                    prog.append((gpu.GATE_NEG, 0, 0))
-                elif rng.random() < 0.7:
-                    max_rot = max(1, (n - 1) // rot_scale)
-                    r_lo = -min(3, max_rot)
-                    r_hi = min(3, max_rot)
-                    prog.append((gpu.GATE_COL, rng.randrange(ncols),
-                                 rng.randrange(r_lo, r_hi + 1)))
-                    depth += 1
-                else:
-                    prog.append((gpu.GATE_CONST, rng.randrange(2), 0))
-                    depth += 1
+            # a tree of exactly the drawn depth, 1..MAX_DEPTH
+            max_rot = min(3, (n - 1) // rot_scale)
+            prog, _ = gate_ref.compile_tree(gate_ref.random_tree(
+                rng, ncols, 2, range(-max_rot, max_rot + 1),
+                rng.randrange(1, gate_ref.MAX_DEPTH + 1)))
             fr_vec = lambda ints: b"".join(
                 oracle.fr_from_canonical(v.to_bytes(32, "little"))
                 for v in ints)
@@ -135,23 +129,8 @@ def main():
             got = [int.from_bytes(
                 oracle.fr_to_canonical(raw[32 * i:32 * (i + 1)]), "little")
                 for i in range(n)]
-            want = []
-            for row in range(n):
-                st = []
-                for op, a_, b_ in prog:
-                    if op == gpu.GATE_COL:
-                        st.append(cols_int[a_][(row + b_ * rot_scale) % n])
-                    elif op == gpu.GATE_CONST:
-                        st.append(consts[a_])
-                    elif op == gpu.GATE_NEG:
-                        st[-1] = (-st[-1]) % R
-                    else:
-                        rhs = st.pop()
-                        lhs = st.pop()
-                        st.append((lhs + rhs) % R if op == gpu.GATE_ADD else
-                                  (lhs - rhs) % R if op == gpu.GATE_SUB else
-                                  lhs * rhs % R)
-                want.append(st[0])
+            want = gate_ref.eval_program(cols_int, consts, prog, n,
+                                         rot_scale)
             for d in d_cols + [d_out]:
                 gpu.free(d)
             assert got == want, (kind, log_n, len(prog))
